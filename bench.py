@@ -12,9 +12,16 @@ over the ranks by contiguous ranges (distributed.shard_range), value = the whole
 second.  `--scaling weak`: every rank scores its own full copy of the config (per-GPU work fixed).  Either way the only
 collective is the k-mer-keyed exchange of the database parts.
 
-`e2e` in the JSON line (rank 0, N = 1): the COLD build of the same workload, wall clock -- new context, matrices uploaded
-from host memory, first scoring call, MIF0 filter, database file written -- i.e. what a one-shot `ipk.py build` pays
-beyond reading its inputs; never part of `value`.
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds what the headline figure does not
+need, each leg after the timed steps: `e2e` (rank 0, N = 1), the COLD build of the same workload, wall clock -- new context,
+matrices uploaded from host memory, first scoring call, MIF0 filter, database file written -- i.e. what a one-shot
+`ipk.py build` pays beyond reading its inputs, with a sample of the loader; `cpu_baseline` + `sample_check` (N = 1), the CPU
+oracle on a bounded sample of the workload and the GPU's counts on the same sample; `e2e_multi` (N > 1), the file stages
+behind a step.  None of them is ever part of `value`.  `--e2e` / `--cpu-groups` set one leg explicitly.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step returned is written as DIR/<name>.npy (float64 for
+integers, float32 for scores; arrays longer than DUMP_MAX_ELEMS are a fixed, seeded sample, with the sampled indices
+beside them).  The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -148,6 +155,67 @@ def multi_rank_file_stages(eng, D, dist, d_logp, groups, k, eps, sigma, cfg, wor
     return res if rank == 0 else None
 
 
+DUMP_MAX_ELEMS = 1 << 20      # per array and rank: at most six arrays of <= 8 MB each
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, obj, output, world, rank):
+    """What the timed path returned in its last step, as DIR/<name>.npy: the key-major database shard (keys, key offsets,
+    entries' branches and scores) or the group-major result (group ids, offsets, keys, scores).  Device arrays longer than
+    the cap are sampled ON the device at seeded indices (sorted, unique; `<name>_index.npy`) -- a shard holds GBs."""
+    import torch
+    from ipk_amd import engine as E
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    cap = max(1, DUMP_MAX_ELEMS // world)
+    written = 0
+
+    def save(name, a):
+        nonlocal written
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+        written += a.nbytes
+
+    def pick(n, salt):
+        if n <= cap:
+            return None
+        return np.unique(np.random.default_rng([DUMP_SEED, salt]).integers(0, n, size=cap, dtype=np.int64))
+
+    def rows(ptr, n, words, idx):
+        """int32 rows [len(idx) or n, words] of n rows of `words` 4-byte words of engine-owned device memory."""
+        if n == 0 or not ptr:
+            return np.zeros((n if idx is None else len(idx), words), np.int32)
+        v = E._device_tensor(ptr, (n, words), "int32", obj)
+        if idx is not None:
+            v = v[torch.from_numpy(idx).to(v.device)]
+        return v.cpu().numpy().reshape(-1, words)
+
+    if output == "group":
+        n = obj.num_entries
+        save("group_ids", obj.group_ids.astype(np.float64))
+        save("group_offsets", obj.offsets.astype(np.float64))
+        ie = pick(n, 1)
+        if ie is not None:
+            save("entry_index", ie.astype(np.float64))
+        save("keys", rows(obj.keys_device_ptr(), n, 1, ie).view(np.uint32).ravel().astype(np.float64))
+        save("scores", rows(obj.scores_device_ptr(), n, 1, ie).view(np.float32).ravel().copy())
+    else:
+        nk, ne = obj.num_keys, obj.num_entries
+        ik = pick(nk, 2)
+        if ik is not None:
+            save("key_index", ik.astype(np.float64))
+        save("keys", rows(obj.keys_device_ptr(), nk, 1, ik).view(np.uint32).ravel().astype(np.float64))
+        # offsets: u64 [nk + 1] -- the sampled keys' first entries, and the total as the last element
+        io = None if ik is None else np.append(ik, nk)
+        save("key_offsets", rows(obj.key_offsets_device_ptr(), nk + 1, 2, io).view(np.uint64).ravel().astype(np.float64))
+        ie = pick(ne, 3)
+        if ie is not None:
+            save("entry_index", ie.astype(np.float64))
+        ent = rows(obj.entries_device_ptr(), ne, 2, ie)
+        save("entry_branches", ent[:, 0].view(np.uint32).astype(np.float64))
+        save("entry_scores", ent[:, 1].view(np.float32).copy())
+    print(f"bench.py: rank {rank} wrote {written / 1e6:.1f} MB of outputs to {out_dir}", file=sys.stderr)
+
+
 def launch_ranks(n, argv):
     """`python3 bench.py --gpus N` without a launcher: this process touches no GPU and starts the N ranks itself -- as a CHILD
     (`python -m torch.distributed.run`, rendezvous on 127.0.0.1), never by exec -- relays their output (rank 0's JSON line) and
@@ -224,13 +292,23 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="override the number of branch groups (0 = config's)")
     ap.add_argument("--alpha", type=float, default=0.0, help="override the column concentration")
     ap.add_argument("--output", default="db", choices=["db", "group"], help="db: key-major database shard; group: per-branch CSR")
-    ap.add_argument("--cpu-groups", type=int, default=-1, help="groups timed on the CPU oracle (-1 = auto, 0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the legs beside the headline figure (cold end-to-end build, loader "
+                    "sample, CPU baseline + sample check with N = 1; file stages with N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned to DIR/<name>.npy")
+    ap.add_argument("--cpu-groups", type=int, default=None, help="groups timed on the CPU oracle (-1 = auto, 0 = skip; default: -1 with --full, else 0)")
     ap.add_argument("--variant", type=int, default=0, help="engine option 'variant' (0 = auto; diagnostics: 1 atomics, 2 chunked pool, 3 exact partition)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="strong: the config's groups split over the ranks; weak: a full copy per rank")
-    ap.add_argument("--e2e", type=int, default=1, help="1: also time the cold end-to-end build (N = 1 only; in a fresh child process); 0: skip")
+    ap.add_argument("--e2e", type=int, default=None, help="1: also time the cold end-to-end build (N = 1: in a fresh child process; "
+                    "N > 1: the file stages); 0: skip (default: 1 with --full, else 0)")
     ap.add_argument("--e2e-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)   # launcher / watchdog rehearsal without a GPU (tests)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("need --steps >= 1 and --warmup >= 0")
+    if args.e2e is None:
+        args.e2e = 1 if args.full else 0
+    if args.cpu_groups is None:
+        args.cpu_groups = -1 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.e2e_child:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -327,7 +405,9 @@ def main():
         want = int(env) if env else D.default_pieces(len(np.unique(groups)))
         n_pieces = D.agree_on_pieces(groups, max(1, want), dist, "cpu" if dist.get_backend() == "gloo" else "cuda")
 
-    def step(record):
+    kept = []                 # --dump-outputs: what the last timed step returned, freed after the timed region
+
+    def step(record, keep=False):
         nonlocal emitted, entries, n_keys, exchange_kind
         if args.output == "group":
             r = eng.score_groups(d_logp, groups, k, eps)      # returns after the device work completed
@@ -341,14 +421,20 @@ def main():
             if record:
                 acc["merge"] += db.time_ms()
                 acc["exchange_exposed"] += getattr(t, "exchange_exposed_ms", 0.0)
-            db.free()
+            if keep:
+                kept.append(db)
+            else:
+                db.free()
         if record:
             acc["score"] += t.time_ms(E.T_SCORE); acc["launches"] += t.time_ms(E.T_SCORE_LAUNCHES)
             acc["total"] += t.time_ms(E.T_TOTAL); acc["compact"] += t.time_ms(E.T_COMPACT); acc["prefix"] += t.time_ms(E.T_PREFIX)
             acc["main"] += t.time_ms(E.T_SCORE_MAIN); acc["reduce"] += t.time_ms(E.T_SCORE_REDUCE)
             if args.output != "group":
                 acc["xp_count"] += t.time_ms(E.T_XP_COUNT); acc["xp_write"] += t.time_ms(E.T_XP_WRITE); acc["km_write"] += t.time_ms(E.T_KM_WRITE)
-        t.free()
+        if keep and args.output == "group":
+            kept.append(t)
+        else:
+            t.free()
 
     # engine initialisation (untimed, like data generation): the first call of a context allocates and calibrates its
     # workspaces -- hipMalloc of the multi-GB pair pool sporadically takes seconds
@@ -370,8 +456,8 @@ def main():
         step(False)
     barrier()
     t_start = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for i in range(args.steps):
+        step(True, keep=bool(args.dump_outputs) and i == args.steps - 1)
     barrier()
     last_kernel = eng.last_main_kernel()
     tables_compressed = eng.last_tables_compressed()
@@ -395,6 +481,9 @@ def main():
     else:
         emitted_all = emitted
         n_ranks_seen = 1
+    if kept:
+        dump_outputs(args.dump_outputs, kept[0], args.output, world, rank)
+        kept.pop().free()
 
     # Several ranks, after the timed region: what the rest of a build costs on top of a step -- filter values on every rank's shard,
     # the shards written as files, rank 0's merge of the shard files (merge_stage2's role, db_builder.cpp:392-458).  Warm, not cold.

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                          "--groups", "6", "--cpu-groups", "2"], capture_output=True, text=True, timeout=600)
+                          "--groups", "6", "--cpu-groups", "2", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -43,6 +43,37 @@ def test_bench_weak_mode_and_group_output():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["scaling"] == "weak" and d["value"] > 0 and "e2e" not in d
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline figure and no side legs; --dump-outputs writes the last timed step's
+    database shard, identical from run to run, and (entries beyond the cap) as a seeded sample."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"run{run}"
+        out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--groups", "4", "--dump-outputs", str(d_out)], timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["metric"] == "scored phylo-k-mers/sec" and d["unit"] == "phylo-k-mers/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        for leg in ("e2e", "cpu_baseline", "sample_check", "e2e_multi"):
+            assert leg not in d, leg
+        files = {p.name: np.load(p) for p in d_out.glob("*.npy")}
+        assert {"keys", "key_offsets", "entry_branches", "entry_scores"} <= {n[:-4] for n in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        n_ent = d["config"]["branch_kmer_entries_per_gpu"]
+        assert files["key_offsets.npy"][-1] == n_ent
+        if "entry_index.npy" in files:                         # sampled: the scores of the listed entries
+            assert len(files["entry_scores.npy"]) == len(files["entry_index.npy"]) and files["entry_index.npy"][-1] < n_ent
+        else:
+            assert len(files["entry_scores.npy"]) == n_ent
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def _run_bench(argv, env=None, timeout=300):
@@ -76,7 +107,7 @@ def test_bench_watchdog_ends_a_hung_job_with_an_error():
 def test_bench_two_ranks_on_one_gpu_self_launched():
     """The N > 1 bench path end to end on a one-GPU box: both ranks pinned to GPU 0, gloo transport (RCCL refuses two ranks
     on one device), started by bench.py itself."""
-    out = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--groups", "12"],
+    out = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--groups", "12", "--full"],
                      env={"IPK_BENCH_DEVICE": "0", "IPK_DIST_BACKEND": "gloo"}, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@ TAG=$1
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out
 cd $ROOT
-timeout -k 10 300 python3 bench.py --config cfg4 --steps 3 --warmup 1 --e2e 0 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 300 python3 bench.py --config cfg4 --steps 3 --warmup 1 --full --e2e 0 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/${TAG}_ks
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks -- python3 $ROOT/bench.py --config cfg4 --steps 3 --warmup 1 --cpu-groups 0 --e2e 0 > $OUT/${TAG}_ks.log 2>&1

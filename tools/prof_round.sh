@@ -8,10 +8,10 @@ OUT=$ROOT/gpurun_out
 cd $ROOT
 if [[ $PART == *a* ]]; then
 B="timeout -k 10 300 python3 bench.py"
-$B --steps 20 --warmup 3 > $OUT/${R}_cfg2_bench.json 2> $OUT/${R}_cfg2_bench.err
+$B --steps 20 --warmup 3 --full > $OUT/${R}_cfg2_bench.json 2> $OUT/${R}_cfg2_bench.err
 $B --groups 125 --steps 20 --warmup 3 --e2e 0 --cpu-groups 0 > $OUT/${R}_cfg2_125groups_bench.json 2> /dev/null
 $B --config cfg3 --groups 125 --steps 10 --warmup 2 --e2e 0 --cpu-groups 0 > $OUT/${R}_cfg3_125groups_bench.json 2> /dev/null
-$B --config cfg4 --steps 5 --warmup 1 > $OUT/${R}_cfg4_bench.json 2> $OUT/${R}_cfg4_bench.err
+$B --config cfg4 --steps 5 --warmup 1 --full > $OUT/${R}_cfg4_bench.json 2> $OUT/${R}_cfg4_bench.err
 $B --config cfg5 --steps 10 --warmup 2 --e2e 0 --cpu-groups 0 > $OUT/${R}_cfg5_bench.json 2> /dev/null
 $B --output group --steps 10 --warmup 2 --e2e 0 --cpu-groups 0 > $OUT/${R}_cfg2_group_bench.json 2> /dev/null
 bash tools/sweep_groups.sh 2 8 32 125 250 500 1000 > $OUT/${R}_cfg2_sweep_groups.txt 2>&1
