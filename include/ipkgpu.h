@@ -22,9 +22,13 @@
  * stream that produced them (hipStreamSynchronize / hipEventSynchronize) first.  Every call returns
  * after its device work has finished, so results may be read from any stream afterwards.
  *
- * Not supported (IPKGPU_ERR_INVALID, never a silent fallback): DNA k > 14, amino acids k > 6 (the reference's
- * command line advertises k <= 31, ipk.py:116; its key type here is u32: DNA k <= 16) -- at DNA k = 13, 14 also a
- * call in which one window's half list (its 6- / 7-symbol prefixes or suffixes above their threshold) exceeds 6144
+ * Not supported (IPKGPU_ERR_INVALID, never a silent fallback): in one call over the whole key space DNA k > 14, amino
+ * acids k > 6 (the reference's command line advertises k <= 31, ipk.py:116; its key type here is u32: DNA k <= 16).
+ * DNA k = 15, 16 are built in key-range passes instead (ipkgpu_score_groups_keyrange_device: the k-mers of one class of
+ * leading symbols per call, one owner; each pass' shard written as a file of its own, the files merged by
+ * ipkgpu_db_merge_files) -- not on several ranks (owners inside a key range would need a slot mapping of their own), not
+ * through the per-branch result or the positions path, not for amino acids k = 7 (35-bit keys).  At DNA k >= 13 also
+ * a call in which one window's half list (its 6- to 8-symbol prefixes or suffixes above their threshold) exceeds 6144
  * entries: near-uniform columns, which real posteriors do not have -- and the reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group
  * files merged later): groups are batched by device memory instead ("workspace_bytes") and the k-mer-keyed
  * merge of batches / ranks runs on the device (ipkgpu_merge_parts*).
@@ -122,8 +126,11 @@ uint32_t ipkgpu_bits_per_symbol(uint32_t sigma);
 /* ipk::kmer_batch -- branch_group.cpp:104-107. */
 size_t ipkgpu_kmer_batch(uint32_t key, size_t n_ranges);
 
-/* Largest supported k for an alphabet (DNA: 14, AA: 6); 0 for unsupported sigma. */
+/* Largest k that one call covering the whole key space accepts (DNA: 14, AA: 6); 0 for unsupported sigma. */
 uint32_t ipkgpu_max_k(uint32_t sigma);
+/* Largest k buildable in key-range passes (ipkgpu_score_groups_keyrange_device): 16 for DNA (u32 keys), = ipkgpu_max_k for
+ * amino acids (no key-range passes: AA k = 7 needs 35-bit keys). */
+uint32_t ipkgpu_max_k_keyrange(uint32_t sigma);
 
 /* ---- the hot path ---------------------------------------------------------------------- */
 
@@ -209,6 +216,21 @@ void ipkgpu_result_free(ipkgpu_result* r);
 int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
                                         uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
                                         uint32_t n_owners, ipkgpu_parts** out);
+/*
+ * Key-range pass (DNA k = 14..16 built in pieces): as ipkgpu_score_groups_keymajor_device with one owner, for only the k-mers
+ * whose first `lead_symbols` symbols spell `lead_class` (base sigma, first symbol most significant).  Those are the keys
+ * [lead_class * sigma^(k - lead_symbols), (lead_class + 1) * sigma^(k - lead_symbols)): the key space of the call is
+ * sigma^(k - lead_symbols) slots, slot q standing for key ipkgpu_parts_key_base(parts) + q.  The restriction is applied where
+ * the leading symbols enter a window's left half list, so a pass scores only its own k-mers; sets and scores equal those of a
+ * whole-key-space call restricted to the range.  ipkgpu_db_from_parts materialises the keys; one database per pass.
+ * Supported: DNA, lead_symbols >= 1, 13 <= k - lead_symbols <= 14, i.e. (k, lead_symbols) in (14,1) (15,1) (15,2) (16,2) (16,3);
+ * anything else is IPKGPU_ERR_INVALID.  A window whose half list exceeds the big-list cap fails the call, as at k = 13, 14.
+ */
+int ipkgpu_score_groups_keyrange_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                        uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                        uint32_t lead_symbols, uint32_t lead_class, ipkgpu_parts** out);
+/* lead_class * sigma^(k - lead_symbols) for key-range parts; 0 for other parts */
+uint64_t ipkgpu_parts_key_base(const ipkgpu_parts* p);
 uint32_t ipkgpu_parts_num_owners(const ipkgpu_parts* p);
 uint64_t ipkgpu_parts_slots(const ipkgpu_parts* p);
 const uint32_t* ipkgpu_parts_counts_device(const ipkgpu_parts* p);
@@ -262,7 +284,8 @@ double ipkgpu_xfer_exposed_ms(const ipkgpu_xfer* x);
 void ipkgpu_xfer_free(ipkgpu_xfer* x);
 
 /* Single-GPU shortcut (n_owners == 1): the parts already ARE the database; produces the key list and
- * MOVES the entry array out of `parts` (which stays valid for its counts/timings, entries become NULL). */
+ * MOVES the entry array out of `parts` (which stays valid for its counts/timings, entries become NULL).
+ * Key-range parts give the keys of their range (key_base + slot); k is the k-mer length of the pass. */
 int ipkgpu_db_from_parts(ipkgpu_ctx* ctx, ipkgpu_parts* parts, uint32_t sigma, uint32_t k, ipkgpu_db** out);
 uint64_t ipkgpu_db_num_keys(const ipkgpu_db* d);
 uint64_t ipkgpu_db_num_entries(const ipkgpu_db* d);

@@ -41,7 +41,8 @@ def ipk():
 @click.option("--write-reduction", type=click.Path(), help="(ignored)")
 @click.option("-a", "--alpha", type=float, default=1.0, show_default=True, help="(ignored) AR gamma shape")
 @click.option("-c", "--categories", type=int, default=4, show_default=True, help="(ignored) AR rate categories")
-@click.option("-k", "--k", "k", type=int, default=8, show_default=True, help="k-mer length (DNA <= 14, AA <= 6 on this engine)")
+@click.option("-k", "--k", "k", type=int, default=8, show_default=True,
+              help="k-mer length (DNA <= 16, AA <= 6 on this engine; DNA k = 15, 16 are built in key-range passes, on one GPU)")
 @click.option("-m", "--model", default=None, help="(ignored) AR model")
 @click.option("--convert-uo", is_flag=True, help="(ignored)")
 @click.option("--no-reduction", is_flag=True, help="(ignored)")
@@ -70,12 +71,15 @@ def ipk():
               help="TSV: AR node label <TAB> branch post-order id, one line per ghost node (instead of the tree-derived plan)")
 @click.option("--num-tree-nodes", type=int, default=0, help="node count of the original tree (MIF0's N, db_builder.cpp:261); default: the reference tree's, or branch groups + 1 with --mapping")
 @click.option("--device", type=int, default=None, help="GPU index [0; LOCAL_RANK under torchrun]")
+@click.option("--key-passes", type=int, default=None,
+              help="build the database in this many key-range passes (4^j; DNA k = 14..16), one pass' k-mers in device memory at a "
+                   "time [auto: one call up to k = 14, 4^(k-14) passes above]")
 def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, alpha, categories, k, model, convert_uo,
           no_reduction, reduction_ratio, omega, filter_, mu, ghosts, use_unrooted, merge_branches, ar_dir, ar_only,
-          ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device):
+          ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device, key_passes):
     """Computes a database of phylo-k-mers from precomputed ancestral probabilities."""
     import ipk_amd
-    from ipk_amd import dbfile, distributed
+    from ipk_amd import dbfile, distributed, keyrange
     from ipk_amd.loader import AncestralProbs
 
     if keep_positions and states == "nucl":
@@ -87,8 +91,17 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
         raise click.UsageError("--merge-branches is not supported (the reference only guards it, main.cpp:31-37)")
     from ipk_amd import tree as T
     sigma = 4 if states == "nucl" else 20
-    if not 2 <= k <= ipk_amd.max_k(sigma):
-        raise click.UsageError(f"k must be in [2, {ipk_amd.max_k(sigma)}] for --states {states} on this engine")
+    if not 2 <= k <= ipk_amd.max_k_keyrange(sigma):
+        raise click.UsageError(f"k must be in [2, {ipk_amd.max_k_keyrange(sigma)}] for --states {states} on this engine")
+    # k beyond one call's key space (DNA 15, 16) or --key-passes: key-range passes (ipk_amd/keyrange.py), one process
+    use_passes = k > ipk_amd.max_k(sigma) or key_passes is not None
+    if use_passes and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError(f"k = {k} / --key-passes: key-range passes run on ONE GPU (several ranks: k <= {ipk_amd.max_k(sigma)})")
+    if use_passes:
+        try:
+            keyrange.plan(sigma, k, key_passes)
+        except ValueError as e:
+            raise click.UsageError(f"--key-passes: {e}")
     os.makedirs(workdir, exist_ok=True)
     output = output or os.path.join(workdir, "DB.ipk")
 
@@ -164,6 +177,20 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     t_load = time.time() - t0
     log_eps = ipk_amd.log_threshold(omega, sigma, k)
     eng = ipk_amd.Engine(device)
+    if use_passes:
+        n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
+        kr = keyrange.build_db_file(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, output, workdir,
+                                    "DNA", tree_index, newick, omega, filter_, n_nodes, key_passes)
+        if verbosity:
+            # the reference's three stage timers (db_builder.cpp:236,290,336), summed over the passes
+            n = kr["passes"]
+            click.echo(f"Loaded {len(labels)} node matrices ({arp.sites} sites) in {t_load * 1e3:.0f} ms")
+            click.echo(f"Computation time: {kr['score_s'] * 1e3:.0f} ms ({kr['emitted']} scored phylo-k-mers; {n} key-range passes)")
+            click.echo(f"Filtering time: {kr['filter_s'] * 1e3:.0f} ms ({n} key-range passes)")
+            click.echo(f"Merge time: {(kr['write_s'] + kr['merge_s']) * 1e3:.0f} ms ({n} pass files written and merged)")
+            click.echo(f"Output: {output} ({kr['totals'][0]} k-mers, {kr['totals'][1]} entries)")
+        eng.close(); arp.close()
+        return
     t0 = time.time()
     if world > 1:
         import torch

@@ -27,6 +27,7 @@
 namespace ipkgpu {
 
 constexpr __host__ __device__ uint32_t ipow(uint32_t b, int e) { return e <= 0 ? 1u : b * ipow(b, e - 1); }
+constexpr __host__ __device__ uint64_t ipow64(uint64_t b, int e) { return e <= 0 ? 1ull : b * ipow64(b, e - 1); }
 constexpr __host__ __device__ uint32_t umin_c(uint32_t a, uint32_t b) { return a < b ? a : b; }
 constexpr __host__ __device__ uint32_t umax_c(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
@@ -103,6 +104,7 @@ struct WinCtx {
     const float* cols;   // [tile_cols][SIGMA]
     const float* best;   // [tile_cols + 1]
     uint32_t w;
+    uint32_t lead_c = 0; // key-range calls (Node's LN > 0): the base-sigma value of the k-mers' first LN symbols
 };
 
 // ---- direct evaluation of a small node: candidate `cand` in [0, SIGMA^H) ------------------
@@ -134,8 +136,8 @@ struct Direct {
 // what a node needs past its own result region.
 template <int SIGMA, int H, int CAP>
 struct Geo {
-    static constexpr uint32_t FULL = ipow(SIGMA, H);
-    static constexpr uint32_t CAPH = umin_c(FULL, (uint32_t)CAP);
+    static constexpr uint64_t FULL = ipow64(SIGMA, H);             // (64-bit: 4^16 = 2^32 is a whole DNA k = 16 window)
+    static constexpr uint32_t CAPH = (uint32_t)(FULL < (uint64_t)CAP ? FULL : (uint64_t)CAP);
     static constexpr bool DIRECT = FULL <= 64;
     static constexpr int HL = H / 2, HR = H - H / 2;
     static constexpr uint32_t scratch()
@@ -220,7 +222,11 @@ __device__ __forceinline__ uint32_t join_to_list(const uint2* L, uint32_t nL, co
 }
 
 // Builds S(J, H, eps) of the window into out[0 .. CAPH); children/scratch follow at out + CAPH.
-template <int SIGMA, int J, int H, int CAP>
+// LN > 0 (key-range calls): only the members whose symbols at window positions [0, LN) spell c.lead_c, coded relative to
+// that class (code - lead_c * sigma^(K - LN) once joined up to the half list).  The restriction is applied where those
+// symbols enter, in the direct leaves; every bound (eps) depends only on the column maxima, so the members kept are exactly
+// the unrestricted ones of that class, with the same scores.
+template <int SIGMA, int J, int H, int CAP, int LN = 0>
 struct Node {
     using G = Geo<SIGMA, H, CAP>;
     static __device__ __forceinline__ uint32_t build(const WinCtx& c, float eps, uint2* out)
@@ -229,9 +235,17 @@ struct Node {
             const uint32_t lane = lane_id();
             float s = 0.f;
             bool pass = false;
+            uint32_t code = lane;
             if (lane < G::FULL) pass = Direct<SIGMA, J, H>::eval(c, eps, lane, s);
+            if constexpr (LN > J) {
+                constexpr int D = LN - J < H ? LN - J : H;           // class symbols inside this leaf (its leading D)
+                constexpr uint32_t LOW = ipow(SIGMA, H - D);
+                const uint32_t v = (c.lead_c / ipow(SIGMA, LN - J - D)) % ipow(SIGMA, D);
+                pass = pass && lane / LOW == v;
+                code = lane - v * LOW;
+            }
             const uint64_t m = __ballot(pass);
-            if (pass) out[mbcnt(m)] = make_uint2(lane, __float_as_uint(s));
+            if (pass) out[mbcnt(m)] = make_uint2(code, __float_as_uint(s));
             return (uint32_t)__popcll(m);                   // FULL <= 64: cannot overflow
         } else {
             constexpr int HL = G::HL, HR = G::HR;
@@ -240,9 +254,9 @@ struct Node {
             const float eps_r = eps - (c.best[c.w + J + HL] - c.best[c.w + J]);       // :55
             uint2* lp = out + G::CAPH;
             uint2* rp = lp + GL::CAPH;
-            const uint32_t nl = Node<SIGMA, J, HL, CAP>::build(c, eps_l, lp);
+            const uint32_t nl = Node<SIGMA, J, HL, CAP, LN>::build(c, eps_l, lp);
             if (nl == LIST_OVERFLOW || nl == 0) return nl;
-            const uint32_t nr = Node<SIGMA, J + HL, HR, CAP>::build(c, eps_r, rp);
+            const uint32_t nr = Node<SIGMA, J + HL, HR, CAP, LN>::build(c, eps_r, rp);
             if (nr == LIST_OVERFLOW || nr == 0) return nr;
             wave_lds_sync();
             const uint32_t n = join_to_list(lp, nl, rp, nr, eps, ipow(SIGMA, HR), out, G::CAPH);
@@ -255,8 +269,9 @@ struct Node {
 // Builds the two top-level half lists of a window of length K (K not DIRECT) in `scratch`
 // (wave_scratch_entries<SIGMA,K,CAP>() entries): L = S(0, K/2, eps - M(right)) at scratch[0..],
 // R = S(K/2, K-K/2, eps - M(left)) right after L's region.  L is built first, with its children
-// over the not-yet-used R region.  Returns false when a list overflowed CAP.
-template <int SIGMA, int K, int CAP>
+// over the not-yet-used R region.  Returns false when a list overflowed CAP.  LN > 0: L holds only the class c.lead_c of its
+// first LN symbols, coded relative to it (Node).
+template <int SIGMA, int K, int CAP, int LN = 0>
 __device__ __forceinline__ bool build_halves(const WinCtx& c, float eps, uint2* scratch,
                                              const uint2*& Lp, uint32_t& nL, const uint2*& Rp, uint32_t& nR)
 {
@@ -267,7 +282,8 @@ __device__ __forceinline__ bool build_halves(const WinCtx& c, float eps, uint2* 
     uint2* lp = scratch;
     uint2* rp = scratch + GL::CAPH;
     Lp = lp; Rp = rp; nL = 0; nR = 0;
-    const uint32_t nl = Node<SIGMA, 0, HL, CAP>::build(c, eps_l, lp);
+    static_assert(LN >= 0 && LN < HL, "the class symbols lie inside the left half");
+    const uint32_t nl = Node<SIGMA, 0, HL, CAP, LN>::build(c, eps_l, lp);
     if (nl == LIST_OVERFLOW) return false;
     if (nl == 0) return true;
     const uint32_t nr = Node<SIGMA, HL, HR, CAP>::build(c, eps_r, rp);

@@ -183,6 +183,8 @@ struct ipkgpu_parts {
     // one owner, one batch: the database's key list (the non-empty slots and their entry offsets) is built inside the scoring
     // call, ahead of the key-major writer -- ipkgpu_db_from_parts then only hands the arrays over
     uint32_t* pre_keys = nullptr; uint64_t* pre_key_off = nullptr; uint64_t pre_n_keys = 0; double t_keys = 0;
+    uint32_t lead = 0;                        // key-range parts (ipkgpu_score_groups_keyrange_device): slot q stands for key key_base + q
+    uint64_t key_base = 0;
     double t_total = 0, t_prefix = 0, t_score = 0, t_compact = 0, t_main = 0, t_reduce = 0, t_count = 0, t_write = 0, t_km = 0;
     int score_launches = 0;
 };
@@ -340,6 +342,7 @@ extern "C" {
 
 uint32_t ipkgpu_bits_per_symbol(uint32_t sigma) { return sigma == 4 ? 2u : sigma == 20 ? 5u : 0u; }
 uint32_t ipkgpu_max_k(uint32_t sigma) { return sigma == 4 ? 14u : sigma == 20 ? 6u : 0u; }
+uint32_t ipkgpu_max_k_keyrange(uint32_t sigma) { return sigma == 4 ? 16u : ipkgpu_max_k(sigma); }
 size_t ipkgpu_kmer_batch(uint32_t key, size_t n_ranges) { return n_ranges ? key % n_ranges : 0; }
 
 float ipkgpu_log_threshold(float omega, uint32_t sigma, uint32_t k)
@@ -695,31 +698,32 @@ template <int SIGMA, int K> constexpr uint32_t xp_tbl()
     if (SIGMA == 4 && K >= 13) return 32768u;                           // DNA k = 13, 14: 2048 / 8192 buckets per group (TBL a multiple of 4^7 = a row's code range)
     return stream_tbl<SIGMA, K>();
 }
-template <int SIGMA, int K> uint32_t xp_nb() {
+// KK: the key space of the call is sigma^KK (KK < K: a key-range call, kernels_score.hpp score_xp_kernel); the window's geometry is K's
+template <int SIGMA, int K, int KK = K> uint32_t xp_nb() {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
-    if constexpr (TBL == 0) return 0; else return (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
+    if constexpr (TBL == 0) return 0; else return (uint32_t)((ipow(SIGMA, KK) + TBL - 1) / TBL);
 }
-template <int SIGMA, int K> size_t xp_lds() {
+template <int SIGMA, int K, int KK = K> size_t xp_lds() {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
     if constexpr (TBL == 0) return 0;
     else {
         constexpr int CAP = fast_cap<SIGMA, K>();
-        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
+        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, KK) + TBL - 1) / TBL);
         return TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8 + (size_t)NB * 4;
     }
 }
-template <int SIGMA, int K, bool WRITE>
+template <int SIGMA, int K, bool WRITE, int KK = K>
 int launch_xp(ipkgpu_ctx* ctx, const XpParams& xp, uint32_t n_wg)
 {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
     if constexpr (TBL == 0) { (void)xp; (void)n_wg; return fail(ctx, IPKGPU_ERR_INVALID, "exact-partition variant unsupported for this sigma/k"); }
     else {
         constexpr int CAP = fast_cap<SIGMA, K>();
-        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
+        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, KK) + TBL - 1) / TBL);
         constexpr size_t lds = TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8 + (size_t)NB * 4;
         static_assert(lds <= 160 * 1024, "exact-partition LDS budget");
         static_assert((TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8) % 8 == 0, "cursor alignment");
-        auto kern = score_xp_kernel<SIGMA, K, CAP, XP_TW, xp_nw<SIGMA, K>(), TBL, WRITE>;
+        auto kern = score_xp_kernel<SIGMA, K, CAP, XP_TW, xp_nw<SIGMA, K>(), TBL, WRITE, KK>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(n_wg), dim3(xp_nw<SIGMA, K>() * 64), lds, ctx->stream, xp);
@@ -727,7 +731,7 @@ int launch_xp(ipkgpu_ctx* ctx, const XpParams& xp, uint32_t n_wg)
         return IPKGPU_OK;
     }
 }
-template <int SIGMA, int K, bool WRITE>
+template <int SIGMA, int K, bool WRITE, int KK = K>
 int launch_xp_overflow(ipkgpu_ctx* ctx, const XpParams& xp)
 {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
@@ -737,7 +741,7 @@ int launch_xp_overflow(ipkgpu_ctx* ctx, const XpParams& xp)
     } else {
         constexpr size_t lds = TileGeo<SIGMA, K, 1>::HEAD_BYTES + (size_t)wave_scratch_entries<SIGMA, K, big_capf<SIGMA, K>()>() * 8;
         static_assert(lds + 64 <= 160 * 1024, "big-list (exact partition) LDS budget");
-        auto kern = score_overflow_xp_kernel<SIGMA, K, TBL, WRITE>;
+        auto kern = score_overflow_xp_kernel<SIGMA, K, TBL, WRITE, KK>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(32 / OVF_NW, (160 * 1024) / (lds + 64)));
@@ -746,13 +750,13 @@ int launch_xp_overflow(ipkgpu_ctx* ctx, const XpParams& xp)
         return IPKGPU_OK;
     }
 }
-template <int SIGMA, int K, bool COMPRESS>
+template <int SIGMA, int K, bool COMPRESS, int KK = K>
 int launch_xp_reduce(ipkgpu_ctx* ctx, uint32_t n_gb, uint32_t S, uint64_t T, const uint64_t* off, uint32_t* table)
 {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
     if constexpr (TBL == 0) { (void)n_gb; (void)S; (void)T; (void)off; (void)table; return fail(ctx, IPKGPU_ERR_INVALID, "exact-partition variant unsupported"); }
     else {
-        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
+        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, KK) + TBL - 1) / TBL);
         static_assert(!COMPRESS || NB == 1 || TBL % 64 == 0, "a 64-slot block must not straddle two buckets");
         constexpr int NT = TBL <= 16384 ? 512 : 1024;       // (16000-slot tables: 1024 threads measure the same 16.5 ms as 512 since the coalesced epilogue, 256 are slower: 22.3)
         constexpr size_t lds = COMPRESS ? (size_t)comp_padded_slots<TBL, NT>() * 4 + (NT / 64 + 1) * 4 : (size_t)TBL * 4;
@@ -898,47 +902,80 @@ int dispatch_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const ScorePa
     return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
 }
 
-uint32_t xp_buckets(uint32_t sigma, uint32_t k)
+// Key-range calls (lead > 0 leading symbols fixed): DNA only, the key space of a pass 4^(k - lead) with k - lead in {13, 14}
+// -- the geometry of the k = 13 / 14 exact partition (ipkgpu_score_groups_keyrange_device)
+bool keyrange_supported(uint32_t sigma, uint32_t k, uint32_t lead)
+{
+    return sigma == 4 && lead >= 1 && k > lead && k - lead >= 13 && k - lead <= 14 && k <= 16;
+}
+#define IPK_KR_DISPATCH(K_V, LEAD_V, EXPR_MACRO)                                       \
+    do {                                                                               \
+        switch ((K_V) * 8 + (LEAD_V)) {                                                \
+            case 14 * 8 + 1: EXPR_MACRO(4, 14, 13);                                    \
+            case 15 * 8 + 1: EXPR_MACRO(4, 15, 14); case 15 * 8 + 2: EXPR_MACRO(4, 15, 13); \
+            case 16 * 8 + 2: EXPR_MACRO(4, 16, 14); case 16 * 8 + 3: EXPR_MACRO(4, 16, 13); \
+        }                                                                              \
+    } while (0)
+
+uint32_t xp_buckets(uint32_t sigma, uint32_t k, uint32_t lead = 0)
 {
 #define M_XNB(S_, K_) return xp_nb<S_, K_>()
+#define M_KXNB(S_, K_, KK_) return xp_nb<S_, K_, KK_>()
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXNB); return 0; }
     IPK_DISPATCH(sigma, k, M_XNB);
 #undef M_XNB
+#undef M_KXNB
     return 0;
 }
-size_t xp_lds_bytes(uint32_t sigma, uint32_t k)
+size_t xp_lds_bytes(uint32_t sigma, uint32_t k, uint32_t lead = 0)
 {
 #define M_XLDS(S_, K_) return xp_lds<S_, K_>()
+#define M_KXLDS(S_, K_, KK_) return xp_lds<S_, K_, KK_>()
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXLDS); return 0; }
     IPK_DISPATCH(sigma, k, M_XLDS);
 #undef M_XLDS
+#undef M_KXLDS
     return 0;
 }
-int dispatch_xp(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, uint32_t n_wg, bool write)
+int dispatch_xp(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, uint32_t n_wg, bool write, uint32_t lead = 0)
 {
 #define M_XP(S_, K_) return write ? launch_xp<S_, K_, true>(ctx, xp, n_wg) : launch_xp<S_, K_, false>(ctx, xp, n_wg)
+#define M_KXP(S_, K_, KK_) return write ? launch_xp<S_, K_, true, KK_>(ctx, xp, n_wg) : launch_xp<S_, K_, false, KK_>(ctx, xp, n_wg)
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXP); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
     IPK_DISPATCH(sigma, k, M_XP);
 #undef M_XP
+#undef M_KXP
     return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
 }
-int dispatch_xp_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, bool write)
+int dispatch_xp_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, bool write, uint32_t lead = 0)
 {
 #define M_XO(S_, K_) return write ? launch_xp_overflow<S_, K_, true>(ctx, xp) : launch_xp_overflow<S_, K_, false>(ctx, xp)
+#define M_KXO(S_, K_, KK_) return write ? launch_xp_overflow<S_, K_, true, KK_>(ctx, xp) : launch_xp_overflow<S_, K_, false, KK_>(ctx, xp)
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXO); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
     IPK_DISPATCH(sigma, k, M_XO);
 #undef M_XO
+#undef M_KXO
     return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
 }
 int dispatch_xp_reduce(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t n_gb, uint32_t S, uint64_t T, const uint64_t* off, uint32_t* table,
-                       bool compress)
+                       bool compress, uint32_t lead = 0)
 {
 #define M_XR(S_, K_) return compress ? launch_xp_reduce<S_, K_, true>(ctx, n_gb, S, T, off, table) : launch_xp_reduce<S_, K_, false>(ctx, n_gb, S, T, off, table)
+#define M_KXR(S_, K_, KK_) return compress ? launch_xp_reduce<S_, K_, true, KK_>(ctx, n_gb, S, T, off, table) : launch_xp_reduce<S_, K_, false, KK_>(ctx, n_gb, S, T, off, table)
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXR); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
     IPK_DISPATCH(sigma, k, M_XR);
 #undef M_XR
+#undef M_KXR
     return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
 }
-uint32_t xp_bucket_slots(uint32_t sigma, uint32_t k)
+uint32_t xp_bucket_slots(uint32_t sigma, uint32_t k, uint32_t lead = 0)
 {
 #define M_XT(S_, K_) return xp_tbl_value<S_, K_>()
+#define M_KXT(S_, K_, KK_) return xp_tbl_value<S_, K_>()
+    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXT); return 0; }
     IPK_DISPATCH(sigma, k, M_XT);
 #undef M_XT
+#undef M_KXT
     return 0;
 }
 #ifndef IPK_KMC_RUNS_DEFAULT
@@ -1011,15 +1048,19 @@ struct Plan {
     std::vector<uint32_t> slot_of;     // [n_mats] group index of each matrix
     uint32_t n_groups = 0, nwin = 0, tiles_per_mat = 0, chunks_per_group = 0;
     uint64_t table_size = 0, gpb = 1;  // slots per group table; groups per batch
+    uint32_t lead = 0, lead_c = 0;     // key-range call: the k-mers whose first `lead` symbols spell lead_c (table_size = sigma^(k - lead))
 };
 
 int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
-              const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl)
+              const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl, uint32_t lead = 0, uint32_t lead_c = 0)
 {
     if (!logp || !mat_group) return fail(ctx, IPKGPU_ERR_INVALID, "null input pointer");
     if (sigma != 4 && sigma != 20) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported alphabet size %u (4 or 20)", sigma);
-    if (k < 2 || k > ipkgpu_max_k(sigma))
+    if (lead == 0 && (k < 2 || k > ipkgpu_max_k(sigma)))
         return fail(ctx, IPKGPU_ERR_INVALID, "k=%u out of range [2, %u] for sigma=%u", k, ipkgpu_max_k(sigma), sigma);
+    if (lead != 0 && !keyrange_supported(sigma, k, lead))
+        return fail(ctx, IPKGPU_ERR_INVALID, "no key-range pass of k=%u with %u leading symbols for sigma=%u", k, lead, sigma);
+    pl.lead = lead; pl.lead_c = lead_c;
     if (n_mats == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no matrices");
     if (sites < k) return fail(ctx, IPKGPU_ERR_INVALID, "alignment has %u sites, fewer than k=%u", sites, k);
     pl.n_mats = n_mats; pl.sites = sites; pl.sigma = sigma; pl.k = k; pl.eps = log_eps;
@@ -1035,7 +1076,7 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
         pl.slot_of[i] = it->second;
     }
     pl.n_groups = (uint32_t)pl.group_ids.size();
-    pl.table_size = ipow(sigma, (int)k);
+    pl.table_size = ipow(sigma, (int)(k - lead));        // a key-range call prices its pass' slots, not sigma^k
     pl.chunks_per_group = (uint32_t)((pl.table_size + CHUNK - 1) / CHUNK);
     // groups per batch: what a group keeps resident at once -- its score table and its share of the pair pool (the scored
     // phylo-k-mers of its windows, 8 bytes each, at the rate calibrated by the context's previous call or its pre-pass; a
@@ -1047,7 +1088,7 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
         const double pool_per_group = (double)n_mats / (double)pl.n_groups * (double)pl.nwin * ppw * 8.0 * 1.25;
         // (the exact partition ends in compressed tables, in place in the pool: occupancy bits, ranks and value addresses only -- T / 8 +
         //  T / 16 + T / 8 bytes instead of 4 T; with the dense figure 125 groups of k = 14 were scored in two batches and merged)
-        const uint32_t xnb = xp_buckets(sigma, k);
+        const uint32_t xnb = xp_buckets(sigma, k, lead);
         const bool no_dense = xnb != 0 && (ctx->opt_variant == 4 || (ctx->opt_variant == 0 && stream_buckets(sigma, k) == 0));
         const double per_group = (double)pl.table_size * (no_dense ? 0.3125 : 4.0) + pool_per_group;
         pl.gpb = std::max<uint64_t>(1, (uint64_t)((double)ctx->workspace_bytes / per_group));
@@ -1084,7 +1125,7 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
 {
     (void)nb;
     const uint32_t tiles_per_mat = (pl.nwin + XP_TW - 1) / XP_TW;
-    const size_t lds_bytes = xp_lds_bytes(pl.sigma, pl.k);
+    const size_t lds_bytes = xp_lds_bytes(pl.sigma, pl.k, pl.lead);
     const uint64_t wg_per_cu = std::max<uint64_t>(1, std::min<uint64_t>(32 / (pl.sigma == 20 ? IPK_XPNW : 11), (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
     const uint64_t slots = (uint64_t)ctx->num_cu * wg_per_cu;
     // four rounds of resident workgroups balance the tail; a unit costs only its NB counters
@@ -1113,12 +1154,13 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     xp.stride = stride;
     xp.ovcur = ctx->gbcur.as<uint32_t>();
     xp.start = nullptr;
+    xp.lead_c = pl.lead_c;
 
     Stopwatch sw(ctx->stream, &ctx->events);
     const int ev_a = sw.mark();
-    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, false));
+    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, false, pl.lead));
     const int ev_a2 = sw.mark();
-    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, false));          // reads the queue length on the device
+    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, false, pl.lead));          // reads the queue length on the device
     RC_TRY(scan_u32(ctx, xp.cnt, n_units, ctx->gboff.as<uint64_t>()));
     uint64_t total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->gboff.as<uint64_t>() + n_units, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1145,9 +1187,9 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     }
     sp.pool = ctx->pool.as<uint2>();
     const int ev_c = sw.mark();
-    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, true));
+    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, true, pl.lead));
     const int ev_d0 = sw.mark();
-    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, true));
+    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, true, pl.lead));
     const int ev_d = sw.mark();
     if (compress) {
         RC_TRY(ensure(ctx, ctx->rank, (size_t)gb * (ctx->mask_words / 2) * 4));
@@ -1157,7 +1199,7 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
         RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
     }
     RC_TRY(dispatch_xp_reduce(ctx, pl.sigma, pl.k, (uint32_t)n_gb, stride, pl.table_size, ctx->gboff.as<uint64_t>(),
-                              compress ? nullptr : ctx->table.as<uint32_t>(), compress));
+                              compress ? nullptr : ctx->table.as<uint32_t>(), compress, pl.lead));
     const int ev_e = sw.mark();
     uint32_t too_big = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&too_big, reinterpret_cast<char*>(ctx->small) + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1165,7 +1207,7 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     if (too_big) return fail(ctx, IPKGPU_ERR_INVALID, "a branch group scores 2^32 phylo-k-mers or more in one batch (exact-partition variant: 32-bit offsets inside a group)");
     ctx->mask_valid = true;
     ctx->table_compressed = compress;
-    ctx->comp_nb = XNB; ctx->comp_stride = stride; ctx->comp_tbl = xp_bucket_slots(pl.sigma, pl.k);
+    ctx->comp_nb = XNB; ctx->comp_stride = stride; ctx->comp_tbl = xp_bucket_slots(pl.sigma, pl.k, pl.lead);
     ctx->acc_main_ms += sw.ms(ev_a, ev_a2) + sw.ms(ev_c, ev_d0);
     ctx->acc_count_ms += sw.ms(ev_a, ev_a2); ctx->acc_write_ms += sw.ms(ev_c, ev_d0);
     ctx->acc_reduce_ms += sw.ms(ev_d, ev_e);
@@ -1272,12 +1314,12 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     ctx->mask_valid = false;
     ctx->table_compressed = false;
     const uint32_t NBK = stream_buckets(pl.sigma, pl.k);
-    const uint32_t XNB = xp_buckets(pl.sigma, pl.k);
+    const uint32_t XNB = xp_buckets(pl.sigma, pl.k, pl.lead);
     // variant 0 = default: stream where its per-wave chunk state fits (all DNA k, AA k <= 5), exact partition for
     // AA k=6; 1 = global atomics, 2 = stream (diagnostic flags honoured), 3 = exact partition wherever it exists
     //                 4 = exact partition ending in the compressed table form (the default for AA k=6: no dense tables --
     //                     64 GB less at cfg4, 40 % fewer bytes moved; 90.5 vs 92.0 ms through dense tables)
-    const bool use_xp = XNB != 0 && (ctx->opt_variant == 3 || ctx->opt_variant == 4 || (ctx->opt_variant == 0 && NBK == 0));
+    const bool use_xp = XNB != 0 && (ctx->opt_variant == 3 || ctx->opt_variant == 4 || (ctx->opt_variant == 0 && NBK == 0) || pl.lead != 0);
     const bool xp_compress = use_xp && ctx->opt_variant != 3;
     const bool use_stream = !use_xp && NBK != 0 && NBK <= 2048 && (ctx->opt_variant == 0 || ctx->opt_variant == 2 || ctx->opt_variant == 5 ||
                                                                    ctx->opt_variant == 6 || ctx->opt_variant == 7);
@@ -2080,25 +2122,23 @@ int merge_sources(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, u
     return IPKGPU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
-                                        uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
-                                        uint32_t n_owners, ipkgpu_parts** out)
+// The key-major call; lead > 0: the key-range pass of the k-mers whose first `lead` symbols spell lead_c (one owner)
+int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites, uint32_t sigma, const uint32_t* mat_group,
+                  uint32_t k, float log_eps, uint32_t n_owners, uint32_t lead, uint32_t lead_c, ipkgpu_parts** out)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (n_owners == 0) return fail(ctx, IPKGPU_ERR_INVALID, "n_owners must be >= 1");
+    const uint64_t key_base = lead ? (uint64_t)lead_c * ipow(sigma, (int)(k - lead)) : 0;
     if (n_mats == 0) {
         // a rank without branch groups (more ranks than groups): empty parts, so that it still takes part in the exchange
-        if ((sigma != 4 && sigma != 20) || k < 2 || k > ipkgpu_max_k(sigma)) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
+        if (lead == 0 && ((sigma != 4 && sigma != 20) || k < 2 || k > ipkgpu_max_k(sigma))) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         ipkgpu_parts* e = new (std::nothrow) ipkgpu_parts();
         if (!e) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
-        e->ctx = ctx; e->n_owners = n_owners; e->slots = (ipow(sigma, (int)k) + n_owners - 1) / n_owners;
+        e->ctx = ctx; e->n_owners = n_owners; e->slots = (ipow(sigma, (int)(k - lead)) + n_owners - 1) / n_owners;
+        e->lead = lead; e->key_base = key_base;
         e->owner_off.assign((size_t)n_owners + 1, 0);
         struct EGuard { ipkgpu_parts* r; ~EGuard() { if (r) ipkgpu_parts_free(r); } } eg{e};
         HIP_TRY(ctx, ctx_alloc(ctx, (void**)&e->d_counts, (size_t)n_owners * e->slots * 4));
@@ -2110,7 +2150,7 @@ int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, 
         return IPKGPU_OK;
     }
     Plan pl;
-    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl));
+    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl, lead, lead_c));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t T = pl.table_size;
     const uint32_t P = n_owners;
@@ -2120,6 +2160,7 @@ int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, 
     ipkgpu_parts* parts = new (std::nothrow) ipkgpu_parts();
     if (!parts) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
     parts->ctx = ctx; parts->n_owners = P; parts->slots = slots;
+    parts->lead = lead; parts->key_base = key_base;
     parts->owner_off.assign((size_t)P + 1, 0);
     struct Guard { ipkgpu_parts* r; ~Guard() { if (r) ipkgpu_parts_free(r); } } guard{parts};
 
@@ -2206,9 +2247,9 @@ int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, 
             HIP_TRY(ctx, ctx_alloc(ctx, (void**)&k_keys, slots * 4));
             HIP_TRY(ctx, ctx_alloc(ctx, (void**)&k_off, (slots + 1) * 8));
             const uint32_t nbk = (uint32_t)((slots + 1 + 255) / 256);
-            if (sigma == 4)
+            if (sigma == 4)      // (one owner: key = slot * 1 + "owner", the key range's base -- 0 but for key-range calls)
                 hipLaunchKernelGGL(merge_write_keys_kernel<4>, dim3(nbk), dim3(256), 0, ctx->stream, b.counts, ctx->tmp_b.as<uint64_t>(),
-                                   ctx->offsets.as<uint64_t>(), slots, 0u, 1u, (int)k, k_keys, k_off);
+                                   ctx->offsets.as<uint64_t>(), slots, (uint32_t)key_base, 1u, (int)k, k_keys, k_off);
             else
                 hipLaunchKernelGGL(merge_write_keys_kernel<20>, dim3(nbk), dim3(256), 0, ctx->stream, b.counts, ctx->tmp_b.as<uint64_t>(),
                                    ctx->offsets.as<uint64_t>(), slots, 0u, 1u, (int)k, k_keys, k_off);
@@ -2361,6 +2402,33 @@ int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, 
     return IPKGPU_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                        uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                        uint32_t n_owners, ipkgpu_parts** out)
+{
+    return keymajor_impl(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, n_owners, 0, 0, out);
+}
+
+int ipkgpu_score_groups_keyrange_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                        uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                        uint32_t lead_symbols, uint32_t lead_class, ipkgpu_parts** out)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (out) *out = nullptr;
+    if (!keyrange_supported(sigma, k, lead_symbols))
+        return fail(ctx, IPKGPU_ERR_INVALID, "no key-range pass of k=%u with %u leading symbols for sigma=%u: DNA only, with 1 <= lead "
+                                             "and 13 <= k - lead <= 14, i.e. (k, lead) in (14,1) (15,1) (15,2) (16,2) (16,3)", k, lead_symbols, sigma);
+    if (lead_class >= ipow(sigma, (int)lead_symbols))
+        return fail(ctx, IPKGPU_ERR_INVALID, "lead_class %u out of range [0, %u)", lead_class, ipow(sigma, (int)lead_symbols));
+    return keymajor_impl(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, 1, lead_symbols, lead_class, out);
+}
+
+uint64_t ipkgpu_parts_key_base(const ipkgpu_parts* p) { return p ? p->key_base : 0; }
+
 uint32_t ipkgpu_parts_num_owners(const ipkgpu_parts* p) { return p ? p->n_owners : 0; }
 uint64_t ipkgpu_parts_slots(const ipkgpu_parts* p) { return p ? p->slots : 0; }
 const uint32_t* ipkgpu_parts_counts_device(const ipkgpu_parts* p) { return p ? p->d_counts : nullptr; }
@@ -2465,7 +2533,9 @@ int ipkgpu_db_from_parts(ipkgpu_ctx* ctx, ipkgpu_parts* parts, uint32_t sigma, u
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (!parts || parts->n_owners != 1 || !parts->d_counts) return fail(ctx, IPKGPU_ERR_INVALID, "parts must be single-owner and not yet consumed");
-    if ((sigma != 4 && sigma != 20) || k < 2 || k > ipkgpu_max_k(sigma) || parts->slots != ipow(sigma, (int)k))
+    const bool kr = parts->lead != 0;         // key-range parts: slot q is key key_base + q
+    if ((sigma != 4 && sigma != 20) || k < 2 || (kr ? !keyrange_supported(sigma, k, parts->lead) : k > ipkgpu_max_k(sigma)) ||
+        parts->slots != ipow(sigma, (int)(k - parts->lead)))
         return fail(ctx, IPKGPU_ERR_INVALID, "sigma/k do not match the parts");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ipkgpu_db* db = new (std::nothrow) ipkgpu_db();
@@ -2507,7 +2577,8 @@ int ipkgpu_db_from_parts(ipkgpu_ctx* ctx, ipkgpu_parts* parts, uint32_t sigma, u
     const uint32_t nbk = (uint32_t)((slots + 1 + 255) / 256);
     if (sigma == 4)
         hipLaunchKernelGGL(merge_write_keys_kernel<4>, dim3(nbk), dim3(256), 0, ctx->stream, ctx->counts.as<uint32_t>(),
-                           ctx->offsets.as<uint64_t>(), ctx->tmp_b.as<uint64_t>(), slots, 0u, 1u, (int)k, db->d_keys, db->d_key_off);
+                           ctx->offsets.as<uint64_t>(), ctx->tmp_b.as<uint64_t>(), slots, (uint32_t)parts->key_base, 1u, (int)k, db->d_keys,
+                           db->d_key_off);
     else
         hipLaunchKernelGGL(merge_write_keys_kernel<20>, dim3(nbk), dim3(256), 0, ctx->stream, ctx->counts.as<uint32_t>(),
                            ctx->offsets.as<uint64_t>(), ctx->tmp_b.as<uint64_t>(), slots, 0u, 1u, (int)k, db->d_keys, db->d_key_off);

@@ -1214,6 +1214,7 @@ struct XpParams {
     uint32_t* ovcur;               // [group * NB + bucket] pairs the big-list write pass has placed so far
     const uint32_t* start;         // [(group * S + segment) * NB + bucket] where the unit's range of the bucket starts, relative to
                                    // off[group * NB * stride] (write pass: a workgroup's NB cursors as one contiguous load)
+    uint32_t lead_c = 0;           // key-range calls (KK < K): the class of the k-mers' first K - KK symbols (WinCtx::lead_c)
 };
 
 // start[(g * S + seg) * NB + b] = off[(g * NB + b) * stride + seg] - off[g * NB * stride]: the scan's offsets of one workgroup's
@@ -1233,18 +1234,27 @@ __global__ __launch_bounds__(256) void xp_unit_starts_kernel(const uint64_t* __r
     start[i] = (uint32_t)rel;
 }
 
-template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool WRITE>
+// Key-range calls (KK < K, DNA k = 14..16 in passes): the window's DC geometry is K's, the key space of the call is sigma^KK --
+// the k-mers whose first LN = K - KK symbols spell xp.lead_c, coded relative to that class (keys = code - lead_c * sigma^KK).
+// The restriction enters in L (build_halves' LN); R is the full right half.  Where R's codes span more than one bucket
+// (K = 15, 16: 4^8 codes against 32768-slot buckets) a row's pairs go to NSUB = 2 buckets: R (ascending codes as built) is cut
+// into its two bucket ranges, each joined as a list of its own.
+template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool WRITE, int KK = K>
 __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const StreamParams& p = xp.s;
     using TG = TileGeo<SIGMA, K, TW>;
-    constexpr uint32_t T = ipow(SIGMA, K);
+    constexpr int LN = K - KK;
+    constexpr uint32_t T = ipow(SIGMA, KK);
     constexpr uint32_t NB = (T + TBL - 1) / TBL;
     constexpr uint32_t WS = stream_wave_scratch<SIGMA, K, CAP>();
     constexpr uint32_t mulR = ipow(SIGMA, K - K / 2);
-    static_assert(TBL % mulR == 0, "a row of the final join must stay inside one bucket");
-    constexpr uint32_t RPB = TBL / mulR;                    // rows (L codes) per bucket
+    constexpr uint32_t NSUB = mulR > TBL ? mulR / TBL : 1;  // buckets a row's pairs span
+    static_assert(NSUB == 1 ? TBL % mulR == 0 : (mulR % TBL == 0 && NSUB == 2), "a row's pairs stay inside one bucket, or split in two");
+    static_assert(LN == 0 || !HalvesDD<SIGMA, K>::OK, "key-range calls build their halves with build_halves");
+    static_assert(Geo<SIGMA, K, CAP>::FULL > 64 && WS > 0, "a window's lists need wave scratch (Geo in 64 bits: 4^16 = 2^32)");
+    constexpr uint32_t RPB = NSUB == 1 ? TBL / mulR : 1;    // rows (L codes) per bucket
     using Cursor = uint32_t;                                // count: pairs of the bucket; write: pairs placed so far
     float* cols = reinterpret_cast<float*>(smem);
     float* best = cols + TG::COLS_F;
@@ -1288,12 +1298,12 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
         }
         __syncthreads();
         for (uint32_t w = wave; w < nw; w += NW) {
-            WinCtx c{cols, best, w};
-            const uint2 *L, *R;
-            uint32_t nL, nR;
+            WinCtx c{cols, best, w, xp.lead_c};
+            const uint2 *L, *R_all;
+            uint32_t nL, nR_all;
             bool ok;
-            if constexpr (HalvesDD<SIGMA, K>::OK) ok = build_halves_dd<SIGMA, K, CAP>(c, p.eps, scratch, L, nL, R, nR);
-            else ok = build_halves<SIGMA, K, CAP>(c, p.eps, scratch, L, nL, R, nR);
+            if constexpr (HalvesDD<SIGMA, K>::OK) ok = build_halves_dd<SIGMA, K, CAP>(c, p.eps, scratch, L, nL, R_all, nR_all);
+            else ok = build_halves<SIGMA, K, CAP, LN>(c, p.eps, scratch, L, nL, R_all, nR_all);
             if (!ok) {                                     // big-list window: queued once, by the count pass
                 if (!WRITE && lane == 0) {
                     const uint32_t qi = atomicAdd(p.ovf_count, 1u);
@@ -1301,10 +1311,12 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
                 }
                 continue;
             }
-            if (nL == 0 || nR == 0) continue;
+            if (nL == 0 || nR_all == 0) continue;
             if (p.flags & 4u) continue;                                        // diagnostics: list building only (nothing is counted or written)
             nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)nL);            // wave-uniform by construction: keep them scalar
-            nR = (uint32_t)__builtin_amdgcn_readfirstlane((int)nR);
+            nR_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)nR_all);
+            // the join of L with R, or with R's bucket range `sub` (NSUB > 1)
+            auto join = [&](const uint2* R, uint32_t nR, uint32_t sub) {
             // R sorted by score, descending (rank by counting, in place; ties by position).  fl(a + b) is monotone
             // in b, so the pairs of a row that pass `a.score + b.score > eps` (pk_compute.cpp:90-91) are exactly a
             // PREFIX of the sorted R -- the reference's own loop shape (sort at :61-70, break at the first failure,
@@ -1380,7 +1392,7 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
                     }
                 }
                 if (!vr) cnt = 0;
-                const uint32_t bk = a.x / RPB;
+                const uint32_t bk = NSUB == 1 ? a.x / RPB : a.x * NSUB + sub;
                 if constexpr (!WRITE) {
                     emitted += cnt;
                     if (cnt) atomicAdd(&cur[bk], cnt);
@@ -1435,6 +1447,19 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
                     for (uint32_t r = 0; r < rows; ++r) do_row(r);
                 }
             }
+            };
+            if constexpr (NSUB == 1) {
+                join(R_all, nR_all, 0u);
+            } else {
+                uint32_t n0 = 0;                           // R's entries in a row's first bucket: a prefix (ascending codes)
+                for (uint32_t jb = 0; jb < nR_all; jb += 64) {
+                    const uint32_t j = jb + lane;
+                    n0 += (uint32_t)__popcll(__ballot(j < nR_all && R_all[j].x < TBL));
+                }
+                n0 = to_sgpr(n0);
+                if (n0) join(R_all, n0, 0u);
+                if (n0 < nR_all) join(R_all + n0, nR_all - n0, 1u);
+            }
         }
     }
     if constexpr (!WRITE) {
@@ -1451,17 +1476,19 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
 // the count pass adds a row's passing pairs to that slot (one global atomic per row), the write pass reserves the
 // row's run behind the slot's offset and writes it.  So these pairs, too, are max-reduced in LDS, and nothing
 // touches the tables after the reduce pass.
-template <int SIGMA, int K, uint32_t TBL, bool WRITE>
+template <int SIGMA, int K, uint32_t TBL, bool WRITE, int KK = K>
 __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams xp)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const StreamParams& p = xp.s;
     constexpr int CAPF = big_capf<SIGMA, K>();
-    constexpr uint32_t T = ipow(SIGMA, K);
+    constexpr int LN = K - KK;                              // key-range calls: as score_xp_kernel
+    constexpr uint32_t T = ipow(SIGMA, KK);
     constexpr uint32_t NB = (T + TBL - 1) / TBL;
     constexpr uint32_t mulR = ipow(SIGMA, K - K / 2);
-    static_assert(TBL % mulR == 0, "a row of the final join must stay inside one bucket");
-    constexpr uint32_t RPB = TBL / mulR;
+    constexpr uint32_t NSUB = mulR > TBL ? mulR / TBL : 1;
+    static_assert(NSUB == 1 ? TBL % mulR == 0 : (mulR % TBL == 0 && NSUB == 2), "a row's pairs stay inside one bucket, or split in two");
+    constexpr uint32_t RPB = NSUB == 1 ? TBL / mulR : 1;
     using TG = TileGeo<SIGMA, K, 1>;
     __shared__ uint32_t sh_n[2];
     float* cols = reinterpret_cast<float*>(smem);
@@ -1482,15 +1509,25 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
         __syncthreads();
         const uint2 *L = scratch, *R = scratch + Geo<SIGMA, K / 2, CAPF>::CAPH;
         if (wave == 0) {
-            WinCtx c{cols, best, 0};
+            WinCtx c{cols, best, 0, xp.lead_c};
             uint32_t nL = 0, nR = 0;
-            const bool fits = build_halves<SIGMA, K, CAPF>(c, p.eps, scratch, L, nL, R, nR);      // (cannot overflow at full capacity)
+            const bool fits = build_halves<SIGMA, K, CAPF, LN>(c, p.eps, scratch, L, nL, R, nR);  // (cannot overflow at full capacity)
             if (!fits) { nL = 0; nR = 0; if (lane == 0 && p.big_ovf) atomicOr(p.big_ovf, 1u); }   // capped lists (big_capf): the call fails
             if (lane == 0) { sh_n[0] = nL; sh_n[1] = nR; }
         }
         __syncthreads();
-        const uint32_t nL = sh_n[0], nR = sh_n[1];
-        if (nL == 0 || nR == 0) continue;
+        const uint32_t nL = sh_n[0], nR_all = sh_n[1];
+        if (nL == 0 || nR_all == 0) continue;
+        uint32_t n0 = nR_all;                      // NSUB > 1: R's entries in a row's first bucket (a prefix: ascending codes)
+        if constexpr (NSUB > 1) {
+            n0 = 0;
+            for (uint32_t jb = 0; jb < nR_all; jb += 64) {
+                const uint32_t j = jb + lane;
+                n0 += (uint32_t)__popcll(__ballot(j < nR_all && R[j].x < TBL));
+            }
+        }
+        // the rows of L against R, or against R's bucket range `sub`
+        auto rows = [&](const uint2* R, uint32_t nR, uint32_t sub) {
         // Rows of L in batches of XP_ROWS per wavefront: the batch's counts over one walk of R (a block of R in registers, the rows'
         // values read once), then ONE global atomic instruction for the batch -- lane u reserves row u's run -- where every row used to
         // wait for a returning atomic of its own (and for its offset's load), then the rows' stores.
@@ -1516,7 +1553,7 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
 #pragma unroll
             for (uint32_t u = 0; u < XP_ROWS; ++u)
                 if (lane == u) { my_c = u < nrow ? c[u] : 0u; my_ax = a[u].x; }
-            const uint32_t my_bk = my_ax / RPB;
+            const uint32_t my_bk = NSUB == 1 ? my_ax / RPB : my_ax * NSUB + sub;
             const size_t my_slot = ((size_t)g * NB + my_bk) * xp.stride + (xp.stride - 1);
             if constexpr (!WRITE) {
                 if (my_c) atomicAdd(&xp.cnt[my_slot], my_c);
@@ -1547,6 +1584,13 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
                     }
                 }
             }
+        }
+        };
+        if constexpr (NSUB == 1) {
+            rows(R, nR_all, 0u);
+        } else {
+            if (n0) rows(R, n0, 0u);
+            if (n0 < nR_all) rows(R + n0, nR_all - n0, 1u);
         }
     }
     if constexpr (!WRITE) {

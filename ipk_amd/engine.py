@@ -126,7 +126,16 @@ def kmer_batch(key, n_ranges):
 
 
 def max_k(sigma):
+    """Largest k one call over the whole key space accepts (DNA 14, AA 6)."""
     return int(load_library().ipkgpu_max_k(sigma))
+
+
+def max_k_keyrange(sigma):
+    """Largest k buildable in key-range passes (DNA 16: u32 keys; AA: max_k)."""
+    L = load_library()
+    L.ipkgpu_max_k_keyrange.restype = C.c_uint32
+    L.ipkgpu_max_k_keyrange.argtypes = [C.c_uint32]
+    return int(L.ipkgpu_max_k_keyrange(sigma))
 
 
 class Result:
@@ -302,6 +311,11 @@ def _bind_keymajor(L):
     L.ipkgpu_score_groups_keymajor_device.restype = C.c_int
     L.ipkgpu_score_groups_keymajor_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
                                                       C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_score_groups_keyrange_device.restype = C.c_int
+    L.ipkgpu_score_groups_keyrange_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
+                                                      C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_parts_key_base.restype = C.c_uint64
+    L.ipkgpu_parts_key_base.argtypes = [C.c_void_p]
     L.ipkgpu_parts_num_owners.restype = C.c_uint32
     L.ipkgpu_parts_num_owners.argtypes = [C.c_void_p]
     L.ipkgpu_parts_slots.restype = C.c_uint64
@@ -394,6 +408,7 @@ ABI_SYMBOLS += [
     "ipkgpu_merge_parts_ptrs", "ipkgpu_comm_unique_id", "ipkgpu_comm_init", "ipkgpu_comm_rank", "ipkgpu_comm_world",
     "ipkgpu_exchange_begin", "ipkgpu_exchange_merge", "ipkgpu_xfer_exposed_ms", "ipkgpu_xfer_free",
     "ipkgpu_comm_available", "ipkgpu_comm_prepare",
+    "ipkgpu_max_k_keyrange", "ipkgpu_score_groups_keyrange_device", "ipkgpu_parts_key_base",
 ]
 
 
@@ -406,6 +421,7 @@ class Parts:
         self.slots = int(lib.ipkgpu_parts_slots(handle))
         self.owner_offsets = np.ctypeslib.as_array(lib.ipkgpu_parts_owner_offsets(handle), shape=(self.n_owners + 1,)).copy()
         self.emitted = int(lib.ipkgpu_parts_emitted(handle))
+        self.key_base = int(lib.ipkgpu_parts_key_base(handle))      # key-range parts: slot q is key key_base + q
         self.extra_ms = {}        # timings of further pieces folded into this object (distributed.build_db_shard)
 
     @property
@@ -534,9 +550,10 @@ def _device_tensor(ptr, shape, dtype, owner):
     return t
 
 
-def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None):
+def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None, keyrange=None):
     """Scoring pass with key-major, owner-split output (see include/ipkgpu.h). logp: torch CUDA tensor
-    [n_mats, sites, sigma] float32 or a raw device pointer with explicit shape."""
+    [n_mats, sites, sigma] float32 or a raw device pointer with explicit shape.  keyrange = (lead, cls): the key-range pass of
+    the k-mers whose first `lead` symbols spell `cls` (one owner; ipkgpu_score_groups_keyrange_device)."""
     _bind_keymajor(self._lib)
     mat_group = np.ascontiguousarray(mat_group, dtype=np.uint32)
     keep = None
@@ -556,9 +573,15 @@ def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=
     else:
         ptr = int(logp)
     out = C.c_void_p()
-    rc = self._lib.ipkgpu_score_groups_keymajor_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
-                                                       mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
-                                                       C.c_float(log_eps), n_owners, C.byref(out))
+    if keyrange is not None:
+        lead, cls = keyrange
+        rc = self._lib.ipkgpu_score_groups_keyrange_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
+                                                           mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                           C.c_float(log_eps), lead, cls, C.byref(out))
+    else:
+        rc = self._lib.ipkgpu_score_groups_keymajor_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
+                                                           mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                           C.c_float(log_eps), n_owners, C.byref(out))
     del keep
     if rc != 0:
         raise self._err(rc)
@@ -671,4 +694,13 @@ Engine.exchange_merge = _exchange_merge
 Engine.comm_world = 1
 Engine.comm_rank = 0
 Engine.score_groups_keymajor = _score_groups_keymajor
+
+
+def _score_groups_keyrange(self, logp, mat_group, k, log_eps, lead, cls):
+    """Key-range pass: Parts of the k-mers whose first `lead` symbols spell `cls` (base sigma), key_base set
+    (include/ipkgpu.h, ipkgpu_score_groups_keyrange_device).  logp as for score_groups_keymajor."""
+    return _score_groups_keymajor(self, logp, mat_group, k, log_eps, keyrange=(int(lead), int(cls)))
+
+
+Engine.score_groups_keyrange = _score_groups_keyrange
 Engine.merge_parts = _merge_parts

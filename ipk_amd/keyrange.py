@@ -1,0 +1,105 @@
+"""DNA databases of k = 15, 16 (and k = 14 on request) built in key-range passes.
+
+A DNA k-mer's packed code holds its first symbol in the top bits (pk_compute.cpp:96-104), so the k-mers whose first j
+symbols spell a class c are the contiguous keys [c * 4^(k-j), (c+1) * 4^(k-j)).  One pass scores one class
+(ipkgpu_score_groups_keyrange_device: a key space of 4^(k-j) slots, the geometry of the k = 13 / 14 exact partition),
+its shard is filtered and written as a database file of its own, and the pass files are merged by (filter value, key)
+into the one file (ipkgpu_db_merge_files, the role of merge_stage2, db_builder.cpp:392-458).  Filtering per pass is valid
+because MIF0's value and the random filter's draw are both per k-mer.  Device memory is bounded by one pass.
+"""
+import os
+import time
+
+import numpy as np
+
+from . import dbfile
+from .engine import T_KM_WRITE, T_SCORE_MAIN, T_SCORE_REDUCE, T_TOTAL, score_threshold
+
+KEY_SYMBOLS = (13, 14)            # k - j of a pass: the key spaces of the exact partition's 32768-slot buckets
+MAX_K = 16                        # u32 keys: 2 bits per DNA symbol
+
+
+def allowed_leads(sigma, k):
+    """Leading-symbol counts j a pass may fix at this (sigma, k): DNA, j >= 1, 13 <= k - j <= 14, k <= 16."""
+    if sigma != 4 or k > MAX_K:
+        return []
+    return [j for j in range(1, k) if k - j in KEY_SYMBOLS]
+
+
+def plan(sigma, k, passes=None):
+    """[(lead, class, key_base, span)] of the passes, in key order (contiguous, disjoint, covering 4^k).
+    passes=None: j = k - 14 (4 passes at k = 15, 16 at k = 16); otherwise passes must be 4^j for an allowed j."""
+    leads = allowed_leads(sigma, k)
+    if passes is None:
+        j = k - 14
+        if j not in leads:
+            raise ValueError(f"no default key-range split for sigma={sigma}, k={k}")
+    else:
+        by_count = {sigma ** j: j for j in leads}
+        if passes not in by_count:
+            raise ValueError(f"{passes} key-range passes are not possible at sigma={sigma}, k={k} "
+                             f"(allowed: {sorted(by_count) or 'none'})")
+        j = by_count[passes]
+    span = sigma ** (k - j)
+    return [(j, c, c * span, span) for c in range(sigma ** j)]
+
+
+def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, sequence_type, tree_index, newick, omega,
+                  filter_="mif0", total_num_groups=None, passes=None, keep_pass_files=False):
+    """Scores every pass, writes its filtered shard to workdir/passes/pass<c>.ipk and merges the pass files into `path`.
+    mats: [n_mats, sites, sigma] float32 (numpy or CUDA tensor; uploaded once).  Returns a dict with the totals, `emitted`,
+    the number of passes, stage times summed over the passes (seconds) and per-pass device timings (ms)."""
+    import torch
+
+    steps = plan(sigma, k, passes)
+    if not hasattr(mats, "data_ptr"):
+        mats = torch.from_numpy(np.ascontiguousarray(mats, dtype=np.float32)).cuda()
+    mat_group = np.ascontiguousarray(mat_group, dtype=np.uint32)
+    pdir = os.path.join(workdir, "passes")
+    os.makedirs(pdir, exist_ok=True)
+    thr = score_threshold(omega, sigma, k)
+    n_nodes = total_num_groups or len(np.unique(mat_group)) + 1
+    out = {"passes": len(steps), "lead": steps[0][0], "emitted": 0, "score_s": 0.0, "filter_s": 0.0, "write_s": 0.0,
+           "merge_s": 0.0, "per_pass": []}
+    paths = []
+    for lead, cls, base, span in steps:
+        t0 = time.time()
+        parts = engine.score_groups_keyrange(mats, mat_group, k, log_eps, lead, cls)
+        db = engine.db_from_parts(parts, sigma, k)
+        t1 = time.time()
+        if filter_ == "mif0":
+            db.filter_mif0(engine, n_nodes, thr)
+        else:
+            keys = db.keys()
+            fv = (dbfile.splitmix_unit(keys) if db.num_keys else np.zeros(0)).astype(np.float32)
+            order = np.argsort(dbfile.filter_sort_code(fv, keys), kind="stable")
+        t2 = time.time()
+        file = os.path.join(pdir, f"pass{cls}.ipk")
+        if filter_ == "mif0":
+            dbfile.write_db_device(engine, db, file, sequence_type, [], "", k, omega)
+        else:
+            br, sc = db.entries()
+            dbfile.write_db(file, sequence_type, [], "", k, omega, keys, db.key_offsets(), br, sc, fv, order)
+        t3 = time.time()
+        paths.append(file)
+        out["emitted"] += parts.emitted
+        out["score_s"] += t1 - t0
+        out["filter_s"] += t2 - t1
+        out["write_s"] += t3 - t2
+        out["per_pass"].append({"class": cls, "key_base": base, "keys": db.num_keys, "entries": db.num_entries,
+                                "emitted": parts.emitted, "call_ms": parts.time_ms(T_TOTAL), "score_ms": parts.time_ms(T_SCORE_MAIN),
+                                "reduce_ms": parts.time_ms(T_SCORE_REDUCE), "writer_ms": parts.time_ms(T_KM_WRITE),
+                                "keys_ms": db.time_ms(), "shard_file_s": t3 - t2})
+        db.free()
+        parts.free()
+    t0 = time.time()
+    out["totals"] = dbfile.merge_shard_files(path, sequence_type, tree_index, newick, k, omega, paths)
+    out["merge_s"] = time.time() - t0
+    if not keep_pass_files:
+        for p in paths:
+            os.remove(p)
+        try:
+            os.rmdir(pdir)
+        except OSError:
+            pass
+    return out
