@@ -29,7 +29,8 @@
  * ipkgpu_db_merge_files) -- not on several ranks (owners inside a key range would need a slot mapping of their own), not
  * through the per-branch result or the positions path, not for amino acids k = 7 (35-bit keys).  At DNA k >= 13 also
  * a call in which one window's half list (its 6- to 8-symbol prefixes or suffixes above their threshold) exceeds 6144
- * entries: near-uniform columns, which real posteriors do not have -- and the reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group
+ * entries, by every scoring entry point, ipkgpu_score_groups_positions included: near-uniform columns, which real
+ * posteriors do not have -- and the reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group
  * files merged later): groups are batched by device memory instead ("workspace_bytes") and the k-mer-keyed
  * merge of batches / ranks runs on the device (ipkgpu_merge_parts*).
  */

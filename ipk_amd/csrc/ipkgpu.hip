@@ -1051,8 +1051,10 @@ struct Plan {
     uint32_t lead = 0, lead_c = 0;     // key-range call: the k-mers whose first `lead` symbols spell lead_c (table_size = sigma^(k - lead))
 };
 
+// slot_bytes: what a group's table costs per slot (0: by the variant the call will take -- 4 B dense, 0.3125 B compressed)
 int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
-              const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl, uint32_t lead = 0, uint32_t lead_c = 0)
+              const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl, uint32_t lead = 0, uint32_t lead_c = 0,
+              double slot_bytes = 0.0)
 {
     if (!logp || !mat_group) return fail(ctx, IPKGPU_ERR_INVALID, "null input pointer");
     if (sigma != 4 && sigma != 20) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported alphabet size %u (4 or 20)", sigma);
@@ -1090,7 +1092,8 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
         //  T / 16 + T / 8 bytes instead of 4 T; with the dense figure 125 groups of k = 14 were scored in two batches and merged)
         const uint32_t xnb = xp_buckets(sigma, k, lead);
         const bool no_dense = xnb != 0 && (ctx->opt_variant == 4 || (ctx->opt_variant == 0 && stream_buckets(sigma, k) == 0));
-        const double per_group = (double)pl.table_size * (no_dense ? 0.3125 : 4.0) + pool_per_group;
+        if (slot_bytes <= 0.0) slot_bytes = no_dense ? 0.3125 : 4.0;
+        const double per_group = (double)pl.table_size * slot_bytes + pool_per_group;
         pl.gpb = std::max<uint64_t>(1, (uint64_t)((double)ctx->workspace_bytes / per_group));
     }
     pl.gpb = std::min<uint64_t>(pl.gpb, pl.n_groups);
@@ -1242,6 +1245,28 @@ int stream_batch_check(ipkgpu_ctx* ctx)
     return IPKGPU_OK;
 }
 
+// Capped big-list capacity (DNA k >= 13, kernels_score.hpp big_capf): a window whose half list exceeds BIG_CAP_ENTRIES raises the
+// flag word at ctx->small + 44.  arm_capped points p.big_ovf at it and clears it (null where nothing is capped); check_capped, after
+// the batch's scoring kernels, turns a raised flag into the call's error.
+int arm_capped(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, ScoreParams& p)
+{
+    const bool capped_lists = sigma == 4 && k >= 13;
+    p.big_ovf = capped_lists ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 44) : nullptr;
+    if (capped_lists) HIP_TRY(ctx, hipMemsetAsync(p.big_ovf, 0, 4, ctx->stream));
+    return IPKGPU_OK;
+}
+
+int check_capped(ipkgpu_ctx* ctx, uint32_t k, const ScoreParams& p)
+{
+    if (!p.big_ovf) return IPKGPU_OK;
+    uint32_t hit = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&hit, p.big_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (hit) return fail(ctx, IPKGPU_ERR_INVALID, "a window's half list exceeds %d entries: beyond the capacity of this engine at k = %u "
+                                                  "(the lists of k >= 13 are capped; lower omega's reach or k)", BIG_CAP_ENTRIES, k);
+    return IPKGPU_OK;
+}
+
 // Scores groups [g0, g0 + gb) into ctx->table ([gb][table_size]); *emitted_out = scored phylo-k-mers of the batch.
 // defer: a stream-variant batch may return with its last wait still owed (ctx->pend.active) -- the caller waits on the stream
 // later anyway and then calls score_batch_finish.
@@ -1299,18 +1324,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     p.flags = (uint32_t)(ctx->opt_variant == 99 ? 1 : 0);
     p.mask = nullptr; p.mask_words = 0;
     // capped big-list capacity (DNA k >= 13, kernels_score.hpp big_capf): the flag word, checked at the end of the batch
-    const bool capped_lists = pl.sigma == 4 && pl.k >= 13;
-    p.big_ovf = capped_lists ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 44) : nullptr;
-    if (capped_lists) HIP_TRY(ctx, hipMemsetAsync(p.big_ovf, 0, 4, ctx->stream));
-    auto check_capped = [&]() -> int {
-        if (!capped_lists) return IPKGPU_OK;
-        uint32_t hit = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&hit, p.big_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (hit) return fail(ctx, IPKGPU_ERR_INVALID, "a window's half list exceeds %d entries: beyond the capacity of this engine at k = %u "
-                                                      "(the lists of k >= 13 are capped; lower omega's reach or k)", BIG_CAP_ENTRIES, pl.k);
-        return IPKGPU_OK;
-    };
+    RC_TRY(arm_capped(ctx, pl.sigma, pl.k, p));
     ctx->mask_valid = false;
     ctx->table_compressed = false;
     const uint32_t NBK = stream_buckets(pl.sigma, pl.k);
@@ -1354,7 +1368,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         ctx->acc_main_ms += sw.ms(a, b);
         ctx->main_kernel = "score_tiles_kernel";
-        return check_capped();
+        return check_capped(ctx, pl.k, p);
     }
 
     // ---- stream variant: pass 1 (append pairs) -> chunk index -> pass 2 (LDS reduce) -> big-list windows
@@ -1364,7 +1378,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     p.mask = ctx->mask.as<uint32_t>(); p.mask_words = ctx->mask_words;
     if (use_xp) {
         const int rc = score_batch_xp(ctx, pl, logp_dev, gb, nb, p, XNB, xp_compress);
-        return rc ? rc : check_capped();
+        return rc ? rc : check_capped(ctx, pl.k, p);
     }
 
     // Segments (workgroups) per group.  More workgroups balance the tail of the persistent kernel, but every
@@ -1876,10 +1890,10 @@ int ipkgpu_score_groups_positions(ipkgpu_ctx* ctx, const float* logp, uint32_t n
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     Plan pl;
-    RC_TRY(make_plan(ctx, logp, n_mats, sites, sigma, mat_group, k, log_eps, pl));
+    // dense 8-byte table entries (score, position) whatever the (sigma, k): priced as such against workspace_bytes
+    RC_TRY(make_plan(ctx, logp, n_mats, sites, sigma, mat_group, k, log_eps, pl, 0, 0, 8.0));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((uint64_t)n_mats * pl.nwin >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many windows per group for the position code");
-    pl.gpb = std::max<uint64_t>(1, pl.gpb / 2);                      // 8-byte table entries
     const uint32_t n_groups = pl.n_groups, cpg = pl.chunks_per_group;
 
     ipkgpu_result* res = new (std::nothrow) ipkgpu_result();
@@ -1933,7 +1947,9 @@ int ipkgpu_score_groups_positions(ipkgpu_ctx* ctx, const float* logp, uint32_t n
         p.flags = 0;
         HIP_TRY(ctx, hipMemsetAsync(ctx->table.p, 0, (size_t)gb * pl.table_size * 8, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(p.ovf_count, 0, 4, ctx->stream));
+        RC_TRY(arm_capped(ctx, sigma, k, p));
         RC_TRY(dispatch_score_pos(ctx, sigma, k, p));
+        RC_TRY(check_capped(ctx, k, p));
         res->score_launches += 1;
         const uint32_t n_chunks = gb * cpg;
         hipLaunchKernelGGL(count_chunks64_kernel, dim3(n_chunks), dim3(256), 0, ctx->stream,

@@ -134,7 +134,9 @@ def test_rejects_bad_arguments(engine):
     with pytest.raises(ipk_amd.IpkGpuError):
         engine.score_groups(mats, [0, 0], 10, -4.0)        # sites < k (unguarded in the reference; rejected here)
     with pytest.raises(ipk_amd.IpkGpuError):
-        engine.score_groups(mats, [0, 0], 13, -4.0)        # k above the supported maximum
+        engine.score_groups(mats, [0, 0], 13, -4.0)        # sites < k at k = 13 as well
+    with pytest.raises(ipk_amd.IpkGpuError):
+        engine.score_groups(synth_matrices(2, 16, 4, 0.3, 5), [0, 0], 15, -4.0)   # k above the whole-key-space maximum (14)
     with pytest.raises(ipk_amd.IpkGpuError):
         engine.score_groups(np.zeros((1, 8, 5), np.float32), [0], 4, -4.0)   # unsupported alphabet
 
@@ -325,24 +327,60 @@ def test_exact_partition_is_the_aa_k6_default_and_handles_big_lists(engine):
         engine.set_option("variant", 0)
 
 
-@pytest.mark.parametrize("sigma,k,sites", [(4, 8, 90), (4, 10, 150), (20, 3, 30), (20, 6, 14)])
-def test_keep_positions_variant(engine, sigma, k, sites):
-    """Row a11 (ipk-aa-pos): kept score + position of the FIRST window reaching it."""
-    mats = synth_matrices(5, sites, sigma, 0.1, 70 + k)
-    groups = np.array([4, 9, 4, 9, 2], dtype=np.uint32)          # interleaved matrices, one single-matrix group
-    eps = co.log_threshold(1.5, sigma, k)
+def check_positions_against_oracle(engine, mats, groups, k, eps):
+    """score_groups_positions against explore_group_pos: keys, score bits and positions of every group, the scored count.
+    Returns the result's scoring launch count (IPKGPU_T_SCORE_LAUNCHES)."""
+    groups = np.asarray(groups, dtype=np.uint32)
+    order = list(dict.fromkeys(groups.tolist()))
     res = engine.score_groups_positions(mats, groups, k, eps)
-    assert res.group_ids.tolist() == [4, 9, 2]
+    assert res.group_ids.tolist() == order
     tot = 0
-    for gi, gid in enumerate([4, 9, 2]):
+    for gi, gid in enumerate(order):
         keys, scores, pos, emitted = co.explore_group_pos(mats[groups == gid], k, eps)
         a, b = int(res.offsets[gi]), int(res.offsets[gi + 1])
-        assert np.array_equal(res.keys()[a:b], keys)
-        assert np.array_equal(res.scores()[a:b].view(np.uint32), scores.view(np.uint32))
-        assert np.array_equal(res.positions()[a:b], pos)
+        assert np.array_equal(res.keys()[a:b], keys), f"group {gid}: key sets differ ({b - a} vs {len(keys)})"
+        assert np.array_equal(res.scores()[a:b].view(np.uint32), scores.view(np.uint32)), f"group {gid}: score bits differ"
+        assert np.array_equal(res.positions()[a:b], pos), f"group {gid}: positions differ"
         tot += emitted
     assert res.emitted == tot
+    launches = res.time_ms(4)
     res.free()
+    return launches
+
+
+@pytest.mark.parametrize("sigma,k,sites", [(4, 8, 90), (4, 10, 150), (20, 3, 30), (20, 6, 14), (4, 11, 60), (4, 12, 40), (4, 13, 30),
+                                           (4, 14, 24)])
+def test_keep_positions_variant(engine, sigma, k, sites):
+    """Row a11 (ipk-aa-pos): kept score + position of the FIRST window reaching it, at every k the entry point accepts (DNA
+    k = 13, 14: dense 8-byte tables of 4^k slots, 2 GB a group at k = 14, and the capped big-list capacity)."""
+    mats = synth_matrices(5, sites, sigma, 0.1, 70 + k)
+    groups = np.array([4, 9, 4, 9, 2], dtype=np.uint32)          # interleaved matrices, one single-matrix group
+    check_positions_against_oracle(engine, mats, groups, k, co.log_threshold(1.5, sigma, k))
+
+
+def test_k13_positions_beyond_the_capped_capacity_fail_loudly(engine):
+    """The positions flavour has the same capped big-list capacity from DNA k = 13 (6144 entries a half list): the flat columns
+    of test_k13_lists_beyond_the_capped_capacity_fail_loudly must end in an error, not in a result with k-mers missing."""
+    mats = np.full((2, 14, 4), np.log10(0.25), dtype=np.float32)
+    with pytest.raises(ipk_amd.IpkGpuError):
+        engine.score_groups_positions(mats, np.array([1, 1], dtype=np.uint32), 13, np.float32(-8.0))
+    # the flag is cleared for the next call: the context is still usable and right
+    check_positions_against_oracle(engine, synth_matrices(2, 40, 4, 0.1, 77), [3, 3], 13, co.log_threshold(1.5, 4, 13))
+
+
+def test_positions_tables_fit_the_workspace():
+    """The positions flavour keeps dense 8-byte tables whatever (sigma, k): 20^6 x 8 B = 512 MB a group at AA k = 6, where the other
+    entry points keep compressed ones.  workspace_bytes = 1.2 GB holds two such tables, so six groups take at least three launches."""
+    sigma, k = 20, 6
+    mats = synth_matrices(12, 14, sigma, 0.03, 606)
+    groups = np.repeat(np.arange(6, dtype=np.uint32) + 40, 2)
+    eng = ipk_amd.Engine(0)
+    try:
+        eng.set_option("workspace_bytes", int(1.2e9))
+        launches = check_positions_against_oracle(eng, mats, groups, k, co.log_threshold(1.5, sigma, k))
+        assert launches >= 3, f"{launches:.0f} launches: more than two 512-MB tables resident at once"
+    finally:
+        eng.close()
 
 
 def test_keep_positions_ties_keep_first_window(engine):
@@ -714,6 +752,34 @@ def test_persistent_reduce_of_128_kb_slices(k, n_groups, sites):
             eng.close()
     assert parts_out[0][0] == parts_out[1][0]
     assert np.array_equal(parts_out[0][1], parts_out[1][1]) and np.array_equal(parts_out[0][2], parts_out[1][2])
+    _check_parts_against_oracle(parts_out[0][0], parts_out[0][1], parts_out[0][2], [0, len(parts_out[0][2])], mats, groups, sigma, k, eps)
+
+
+def _check_parts_against_oracle(emitted, counts, entries, owner_offsets, mats, groups, sigma, k, eps):
+    """Host copies of DNA key-major parts (counts [owners, slots]: slot q of owner o is k-mer q * owners + o; entries [n, 2]) against
+    the oracle, every owner's shard entry by entry (tests/db_check.py), and the scored count."""
+    import torch
+    from tests import db_check as dc
+    assert sigma == 4
+    gids = list(dict.fromkeys(np.asarray(groups).tolist()))
+    expect = dc.oracle_digests(lambda gid: mats[np.asarray(groups) == gid], gids, k, eps, sigma, world=len(counts))
+    assert emitted == sum(e.emitted for e in expect.values())
+    oracle = _oracle_group_fn(mats, groups, k, eps)
+    for o, row in enumerate(counts):
+        q = np.flatnonzero(row)
+        keys = (q * len(counts) + o).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum(row[q], dtype=np.int64)])
+        block = entries[int(owner_offsets[o]):int(owner_offsets[o + 1])]
+        dc.check_db(torch.from_numpy(keys), torch.from_numpy(off), torch.from_numpy(np.ascontiguousarray(block)), gids, expect, sigma, k,
+                    owner=o, world=len(counts), oracle=oracle)
+
+
+def _oracle_group_fn(mats, groups, k, eps):
+    """gid -> (keys, score bits) of the oracle: what tests/db_check.py recomputes for the message of a group that differs."""
+    def one(gid):
+        keys, scores, _ = co.explore_group(mats[np.asarray(groups) == gid], k, eps)
+        return keys, scores.view(np.uint32)
+    return one
 
 
 @pytest.mark.parametrize("n_groups,world", [(70, 1), (130, 3), (5, 2)])
@@ -744,6 +810,7 @@ def test_dense_writer_with_line_aligned_stores(n_groups, world):
     assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
     full, emitted = _oracle_db(mats, groups, k, eps)
     assert out[0][0] == emitted and int(out[0][1].sum()) == sum(len(v) for v in full.values())
+    _check_parts_against_oracle(out[0][0], out[0][1], out[0][2], out[0][3], mats, groups, sigma, k, eps)
 
 
 def test_randomised_cases_against_the_oracle(engine):
