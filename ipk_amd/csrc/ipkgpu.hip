@@ -26,6 +26,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <memory>
 #include <vector>
@@ -130,13 +131,13 @@ struct ipkgpu_ctx {
     std::vector<std::pair<void*, size_t>> free_blocks;
     std::unordered_map<void*, size_t> live_blocks;
     size_t cached_bytes = 0, cache_limit = 0;
-    void* small = nullptr;            // emitted (u64) @0, ovf_count (u32) @16
+    void* small = nullptr;            // SMALL_BYTES of per-batch counters and flags, laid out by the SMALL_* offsets (kernels_score.hpp)
     // pinned staging of the small per-batch index uploads (matrix lists, group -> matrices CSR): copied from without a wait;
     // up_done is recorded behind the last copy and waited for only before the staging is written again
     void* h_up = nullptr; size_t h_up_cap = 0; hipEvent_t up_done = nullptr; bool up_pending = false;
     unsigned long long emitted_host = 0; bool emitted_fetched = false;   // the batch's scored-k-mer count, read back with the batch's last wait
     // Read-backs without a wait of their own: pinned words the stream copies into, valid after the NEXT wait on the stream.
-    // h_rb[0..15] = ctx->small (scored k-mers @0, big-list queue length @4, chunk ids drawn @8, pool-exhausted flag @9);
+    // h_rb[0..15] = a copy of ctx->small (word SMALL_X / 4 holds field SMALL_X);
     // h_rb64[RB_OWNER_OFF ..] = a key-major batch's owner offsets (RB_OWNERS_MAX + 1 of them at most).
     uint32_t* h_rb = nullptr;
     EventPool events;
@@ -213,6 +214,9 @@ struct ipkgpu_db {
 
 static std::string g_create_err;
 constexpr size_t RB_BYTES = 4096, RB_OWNER_OFF = 8 /* in 64-bit words */, RB_OWNERS_MAX = 500;
+
+// the field of the context's counter block at byte offset `off` (SMALL_*, kernels_score.hpp)
+template <class T = uint32_t> static T* small_at(const ipkgpu_ctx* ctx, uint32_t off) { return reinterpret_cast<T*>(static_cast<char*>(ctx->small) + off); }
 
 static int fail(ipkgpu_ctx* ctx, int code, const char* fmt, ...)
 {
@@ -376,7 +380,7 @@ int ipkgpu_create(int device_id, ipkgpu_ctx** out)
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) { ctx->workspace_bytes = (int64_t)(free_b / 2); ctx->cache_limit = free_b / 4; }
     else ctx->workspace_bytes = (int64_t)8 << 30;
-    if ((e = hipMalloc(&ctx->small, 64)) != hipSuccess) {
+    if ((e = hipMalloc(&ctx->small, SMALL_BYTES)) != hipSuccess) {
         (void)hipStreamDestroy(ctx->stream);
         delete ctx;
         return fail(nullptr, IPKGPU_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
@@ -503,12 +507,11 @@ int launch_overflow(ipkgpu_ctx* ctx, const ScoreParams& p)
     }
 }
 
-template <int SIGMA, int K>
+template <int SIGMA, int K, bool POS>
 int launch_both(ipkgpu_ctx* ctx, const ScoreParams& p)
 {
-    int rc = launch_score<SIGMA, K>(ctx, p);
-    if (rc) return rc;
-    return launch_overflow<SIGMA, K>(ctx, p);
+    RC_TRY((launch_score<SIGMA, K, POS>(ctx, p)));
+    return launch_overflow<SIGMA, K, POS>(ctx, p);
 }
 
 
@@ -648,7 +651,6 @@ template <int SIGMA, int K> constexpr int quad_tw() { return K <= 10 ? IPK_QTW :
 #define IPK_QROWLANE 0
 #endif
 template <int SIGMA, int K> constexpr bool quad_rowlane() { return K <= 10 ? IPK_QROWLANE != 0 : IPK_QROWLANE12 != 0; }
-inline bool quad_rowlane_rt(uint32_t sigma, uint32_t k) { return sigma == 4 && (k <= 10 ? IPK_QROWLANE != 0 : IPK_QROWLANE12 != 0); }
 // child nodes of one window per wavefront step (kernels_quad.hpp, ONEWIN): k = 11, 12
 #ifndef IPK_QONEWIN12
 #define IPK_QONEWIN12 1
@@ -769,137 +771,21 @@ int launch_xp_reduce(ipkgpu_ctx* ctx, uint32_t n_gb, uint32_t S, uint64_t T, con
         return IPKGPU_OK;
     }
 }
-template <int SIGMA, int K> uint32_t xp_tbl_value() { return xp_tbl<SIGMA, K>(); }
+// ---- run-time (sigma, k) -> compile-time constants ---------------------------------------------------
+template <int V> using int_c = std::integral_constant<int, V>;
 
-#define IPK_DISPATCH(SIGMA_V, K_V, EXPR_MACRO)                                         \
-    do {                                                                               \
-        if ((SIGMA_V) == 4) {                                                          \
-            switch (K_V) {                                                             \
-                case 2: EXPR_MACRO(4, 2); case 3: EXPR_MACRO(4, 3); case 4: EXPR_MACRO(4, 4); \
-                case 5: EXPR_MACRO(4, 5); case 6: EXPR_MACRO(4, 6); case 7: EXPR_MACRO(4, 7); \
-                case 8: EXPR_MACRO(4, 8); case 9: EXPR_MACRO(4, 9); case 10: EXPR_MACRO(4, 10); \
-                case 11: EXPR_MACRO(4, 11); case 12: EXPR_MACRO(4, 12);                \
-                case 13: EXPR_MACRO(4, 13); case 14: EXPR_MACRO(4, 14);                \
-            }                                                                          \
-        } else if ((SIGMA_V) == 20) {                                                  \
-            switch (K_V) {                                                             \
-                case 2: EXPR_MACRO(20, 2); case 3: EXPR_MACRO(20, 3); case 4: EXPR_MACRO(20, 4); \
-                case 5: EXPR_MACRO(20, 5); case 6: EXPR_MACRO(20, 6);                  \
-            }                                                                          \
-        }                                                                              \
-    } while (0)
-
-uint32_t stream_buckets(uint32_t sigma, uint32_t k)
+// f(int_c<SIGMA>, int_c<K>) for the (sigma, k) of a call: DNA k = 2..14, AA k = 2..6
+template <int SIGMA, int K, int KMAX, class F> int with_k(ipkgpu_ctx* ctx, uint32_t k, F& f)
 {
-#define M_NB(S_, K_) return stream_nb<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_NB);
-#undef M_NB
-    return 0;
+    if (k == (uint32_t)K) return f(int_c<SIGMA>{}, int_c<K>{});
+    if constexpr (K < KMAX) return with_k<SIGMA, K + 1, KMAX>(ctx, k, f);
+    else return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k (%u/%u)", (uint32_t)SIGMA, k);
 }
-uint32_t stream_tbl_value(uint32_t sigma, uint32_t k)
+template <class F> int with_sigma_k(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, F&& f)
 {
-#define M_TBLV(S_, K_) return stream_tbl<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_TBLV);
-#undef M_TBLV
-    return 0;
-}
-uint32_t stream_waves(uint32_t sigma, uint32_t k)
-{
-#define M_NWV(S_, K_) return (uint32_t)stream_nw<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_NWV);
-#undef M_NWV
-    return NW;
-}
-uint32_t stream_tile(uint32_t sigma, uint32_t k)
-{
-#define M_TWV(S_, K_) return (uint32_t)stream_tw<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_TWV);
-#undef M_TWV
-    return TW;
-}
-size_t stream_lds_bytes(uint32_t sigma, uint32_t k)
-{
-#define M_LDS(S_, K_) return stream_lds<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_LDS);
-#undef M_LDS
-    return 0;
-}
-int dispatch_stream_pass1(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const StreamParams& sp, uint32_t n_wg)
-{
-#define M_P1(S_, K_) return launch_stream_pass1<S_, K_>(ctx, sp, n_wg)
-    IPK_DISPATCH(sigma, k, M_P1);
-#undef M_P1
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-uint32_t fast_cap_value(uint32_t sigma, uint32_t k)
-{
-#define M_FCAP(S_, K_) return (uint32_t)fast_cap<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_FCAP);
-#undef M_FCAP
-    return 512;
-}
-bool quad_supported(uint32_t sigma, uint32_t k)
-{
-#define M_QOK(S_, K_) return quad_ok<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_QOK);
-#undef M_QOK
-    return false;
-}
-uint32_t quad_waves(uint32_t sigma, uint32_t k)
-{
-#define M_QNW(S_, K_) return (uint32_t)quad_nw<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_QNW);
-#undef M_QNW
-    return NW;
-}
-uint32_t quad_tile(uint32_t sigma, uint32_t k)
-{
-#define M_QTW(S_, K_) return (uint32_t)quad_tw<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_QTW);
-#undef M_QTW
-    return TW;
-}
-size_t quad_lds_bytes(uint32_t sigma, uint32_t k)
-{
-#define M_QLDS(S_, K_) return quad_lds<S_, K_>()
-    IPK_DISPATCH(sigma, k, M_QLDS);
-#undef M_QLDS
-    return 0;
-}
-int dispatch_quad_pass1(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const StreamParams& sp, uint32_t n_wg, bool count_only = false)
-{
-#define M_Q1(S_, K_) return count_only ? launch_quad_pass1<S_, K_, true>(ctx, sp, n_wg) : launch_quad_pass1<S_, K_, false>(ctx, sp, n_wg)
-    IPK_DISPATCH(sigma, k, M_Q1);
-#undef M_Q1
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_stream_pass2(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t n_gb, uint64_t T, uint32_t* table, bool compress)
-{
-#define M_P2(S_, K_) return launch_stream_pass2<S_, K_>(ctx, n_gb, T, table, compress)
-    IPK_DISPATCH(sigma, k, M_P2);
-#undef M_P2
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_score_pos(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const ScoreParams& p)
-{
-#define M_SP(S_, K_) do { int rc_ = launch_score<S_, K_, true>(ctx, p); return rc_ ? rc_ : launch_overflow<S_, K_, true>(ctx, p); } while (0)
-    IPK_DISPATCH(sigma, k, M_SP);
-#undef M_SP
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_stream_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const StreamParams& sp)
-{
-#define M_SO(S_, K_) return launch_stream_overflow<S_, K_>(ctx, sp)
-    IPK_DISPATCH(sigma, k, M_SO);
-#undef M_SO
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const ScoreParams& p)
-{
-#define M_OV(S_, K_) return launch_overflow<S_, K_>(ctx, p)
-    IPK_DISPATCH(sigma, k, M_OV);
-#undef M_OV
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
+    if (sigma == 4) return with_k<4, 2, 14>(ctx, k, f);
+    if (sigma == 20) return with_k<20, 2, 6>(ctx, k, f);
+    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k (%u/%u)", sigma, k);
 }
 
 // Key-range calls (lead > 0 leading symbols fixed): DNA only, the key space of a pass 4^(k - lead) with k - lead in {13, 14}
@@ -908,76 +794,54 @@ bool keyrange_supported(uint32_t sigma, uint32_t k, uint32_t lead)
 {
     return sigma == 4 && lead >= 1 && k > lead && k - lead >= 13 && k - lead <= 14 && k <= 16;
 }
-#define IPK_KR_DISPATCH(K_V, LEAD_V, EXPR_MACRO)                                       \
-    do {                                                                               \
-        switch ((K_V) * 8 + (LEAD_V)) {                                                \
-            case 14 * 8 + 1: EXPR_MACRO(4, 14, 13);                                    \
-            case 15 * 8 + 1: EXPR_MACRO(4, 15, 14); case 15 * 8 + 2: EXPR_MACRO(4, 15, 13); \
-            case 16 * 8 + 2: EXPR_MACRO(4, 16, 14); case 16 * 8 + 3: EXPR_MACRO(4, 16, 13); \
-        }                                                                              \
-    } while (0)
+// f(int_c<SIGMA>, int_c<K>, int_c<KK>) for the exact partition of a call: windows of k symbols over a key space of sigma^KK --
+// KK = k, or k - lead for a key-range call
+template <class F> int with_xp_shape(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t lead, F&& f)
+{
+    if (!lead) return with_sigma_k(ctx, sigma, k, [&](auto S_, auto K_) { return f(S_, K_, K_); });
+    if (sigma == 4) {
+        switch (k * 8 + lead) {
+            case 14 * 8 + 1: return f(int_c<4>{}, int_c<14>{}, int_c<13>{});
+            case 15 * 8 + 1: return f(int_c<4>{}, int_c<15>{}, int_c<14>{});
+            case 15 * 8 + 2: return f(int_c<4>{}, int_c<15>{}, int_c<13>{});
+            case 16 * 8 + 2: return f(int_c<4>{}, int_c<16>{}, int_c<14>{});
+            case 16 * 8 + 3: return f(int_c<4>{}, int_c<16>{}, int_c<13>{});
+        }
+    }
+    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range");
+}
 
-uint32_t xp_buckets(uint32_t sigma, uint32_t k, uint32_t lead = 0)
+// What the templates say about a call's (sigma, k, lead), read once per call.  A key-range call runs only the exact partition:
+// its other fields keep their defaults.
+struct Geometry {
+    uint32_t fast_cap = 0;                         // fast-path half-list capacity
+    uint32_t stream_nb = 0, stream_tbl = 0;        // stream variant: key buckets per group, slots per bucket (0: no stream variant)
+    uint32_t stream_nw = NW, stream_tw = TW;       // its pass-1 kernel: waves per workgroup, windows per tile, LDS bytes
+    size_t stream_lds = 0;
+    bool quad = false;                             // the quad kernel (pass 1 of the stream variant) exists
+    uint32_t quad_nw = NW, quad_tw = TW;
+    size_t quad_lds = 0;
+    uint32_t xp_nb = 0, xp_tbl = 0;                // exact partition: key buckets per group, slots per bucket (0: none)
+    size_t xp_lds = 0;
+};
+
+int fill_geometry(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t lead, Geometry& g)
 {
-#define M_XNB(S_, K_) return xp_nb<S_, K_>()
-#define M_KXNB(S_, K_, KK_) return xp_nb<S_, K_, KK_>()
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXNB); return 0; }
-    IPK_DISPATCH(sigma, k, M_XNB);
-#undef M_XNB
-#undef M_KXNB
-    return 0;
+    if (!lead)
+        RC_TRY(with_sigma_k(ctx, sigma, k, [&](auto S_, auto K_) {
+            g.fast_cap = fast_cap<S_, K_>();
+            g.stream_nb = stream_nb<S_, K_>(); g.stream_tbl = stream_tbl<S_, K_>();
+            g.stream_nw = stream_nw<S_, K_>(); g.stream_tw = stream_tw<S_, K_>(); g.stream_lds = stream_lds<S_, K_>();
+            g.quad = quad_ok<S_, K_>();
+            g.quad_nw = quad_nw<S_, K_>(); g.quad_tw = quad_tw<S_, K_>(); g.quad_lds = quad_lds<S_, K_>();
+            return IPKGPU_OK;
+        }));
+    return with_xp_shape(ctx, sigma, k, lead, [&](auto S_, auto K_, auto KK_) {
+        g.xp_nb = xp_nb<S_, K_, KK_>(); g.xp_tbl = xp_tbl<S_, K_>(); g.xp_lds = xp_lds<S_, K_, KK_>();
+        return IPKGPU_OK;
+    });
 }
-size_t xp_lds_bytes(uint32_t sigma, uint32_t k, uint32_t lead = 0)
-{
-#define M_XLDS(S_, K_) return xp_lds<S_, K_>()
-#define M_KXLDS(S_, K_, KK_) return xp_lds<S_, K_, KK_>()
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXLDS); return 0; }
-    IPK_DISPATCH(sigma, k, M_XLDS);
-#undef M_XLDS
-#undef M_KXLDS
-    return 0;
-}
-int dispatch_xp(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, uint32_t n_wg, bool write, uint32_t lead = 0)
-{
-#define M_XP(S_, K_) return write ? launch_xp<S_, K_, true>(ctx, xp, n_wg) : launch_xp<S_, K_, false>(ctx, xp, n_wg)
-#define M_KXP(S_, K_, KK_) return write ? launch_xp<S_, K_, true, KK_>(ctx, xp, n_wg) : launch_xp<S_, K_, false, KK_>(ctx, xp, n_wg)
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXP); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
-    IPK_DISPATCH(sigma, k, M_XP);
-#undef M_XP
-#undef M_KXP
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_xp_overflow(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const XpParams& xp, bool write, uint32_t lead = 0)
-{
-#define M_XO(S_, K_) return write ? launch_xp_overflow<S_, K_, true>(ctx, xp) : launch_xp_overflow<S_, K_, false>(ctx, xp)
-#define M_KXO(S_, K_, KK_) return write ? launch_xp_overflow<S_, K_, true, KK_>(ctx, xp) : launch_xp_overflow<S_, K_, false, KK_>(ctx, xp)
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXO); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
-    IPK_DISPATCH(sigma, k, M_XO);
-#undef M_XO
-#undef M_KXO
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-int dispatch_xp_reduce(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t n_gb, uint32_t S, uint64_t T, const uint64_t* off, uint32_t* table,
-                       bool compress, uint32_t lead = 0)
-{
-#define M_XR(S_, K_) return compress ? launch_xp_reduce<S_, K_, true>(ctx, n_gb, S, T, off, table) : launch_xp_reduce<S_, K_, false>(ctx, n_gb, S, T, off, table)
-#define M_KXR(S_, K_, KK_) return compress ? launch_xp_reduce<S_, K_, true, KK_>(ctx, n_gb, S, T, off, table) : launch_xp_reduce<S_, K_, false, KK_>(ctx, n_gb, S, T, off, table)
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXR); return fail(ctx, IPKGPU_ERR_INVALID, "unsupported key range"); }
-    IPK_DISPATCH(sigma, k, M_XR);
-#undef M_XR
-#undef M_KXR
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
-}
-uint32_t xp_bucket_slots(uint32_t sigma, uint32_t k, uint32_t lead = 0)
-{
-#define M_XT(S_, K_) return xp_tbl_value<S_, K_>()
-#define M_KXT(S_, K_, KK_) return xp_tbl_value<S_, K_>()
-    if (lead) { if (keyrange_supported(sigma, k, lead)) IPK_KR_DISPATCH(k, lead, M_KXT); return 0; }
-    IPK_DISPATCH(sigma, k, M_XT);
-#undef M_XT
-#undef M_KXT
-    return 0;
-}
+
 #ifndef IPK_KMC_RUNS_DEFAULT
 #define IPK_KMC_RUNS_DEFAULT 1
 #endif
@@ -1000,34 +864,6 @@ CompTable comp_table(const ipkgpu_ctx* ctx)
     return ct;
 }
 
-int dispatch_score(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const ScoreParams& p)
-{
-    if (sigma == 4) {
-        switch (k) {
-            case 2: return launch_both<4, 2>(ctx, p);
-            case 3: return launch_both<4, 3>(ctx, p);
-            case 4: return launch_both<4, 4>(ctx, p);
-            case 5: return launch_both<4, 5>(ctx, p);
-            case 6: return launch_both<4, 6>(ctx, p);
-            case 7: return launch_both<4, 7>(ctx, p);
-            case 8: return launch_both<4, 8>(ctx, p);
-            case 9: return launch_both<4, 9>(ctx, p);
-            case 10: return launch_both<4, 10>(ctx, p);
-            case 11: return launch_both<4, 11>(ctx, p);
-            case 12: return launch_both<4, 12>(ctx, p);
-        }
-    } else if (sigma == 20) {
-        switch (k) {
-            case 2: return launch_both<20, 2>(ctx, p);
-            case 3: return launch_both<20, 3>(ctx, p);
-            case 4: return launch_both<20, 4>(ctx, p);
-            case 5: return launch_both<20, 5>(ctx, p);
-            case 6: return launch_both<20, 6>(ctx, p);
-        }
-    }
-    return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k (%u/%u)", sigma, k);
-}
-
 }  // namespace
 
 // ---- the scoring pass shared by every output form ---------------------------------------------------
@@ -1041,6 +877,37 @@ constexpr int IPKGPU_RETRY_AGAIN = 101;                  // internal: the same b
 #define IPK_OVF_POOL_RATIO 500
 #endif
 
+// What the scoring pass of a call runs.  variant 0 = default: the stream variant where its per-wave chunk state fits (all DNA k <= 12,
+// AA k <= 5), the exact partition ending in compressed tables elsewhere; 1 = tiles kernel with global atomics, 2 = stream variant with
+// the first-generation score_stream_kernel (diagnostic flags honoured), 3 = exact partition wherever it exists, with dense tables,
+// 4 = exact partition ending in the compressed table form (the default for AA k=6: no dense tables -- 64 GB less at cfg4, 40 % fewer
+// bytes moved; 90.5 vs 92.0 ms through dense tables), 5 = stream variant with the quad kernel, 6 / 7 = stream variant with compressed /
+// dense tables.  Key-range calls take the exact partition, positions the tiles kernel.
+enum class PassKind { tiles, stream, quad, xp };
+struct Pass {
+    PassKind kind = PassKind::tiles;
+    bool positions = false;            // tiles kernel with 8-byte (score, position) table entries
+    bool compress = false;             // compressed tables: the exact partition's, or where the stream variant must take them
+    double slot_bytes() const { return positions ? 8.0 : kind == PassKind::xp && compress ? 0.3125 : 4.0; }
+};
+
+Pass choose_pass(int64_t variant, uint32_t sigma, uint32_t lead, bool positions, const Geometry& g)
+{
+    Pass ps;
+    ps.positions = positions;
+    if (positions) return ps;
+    const int64_t v = variant;
+    if (g.xp_nb != 0 && (v == 3 || v == 4 || (v == 0 && g.stream_nb == 0) || lead != 0)) {
+        ps.kind = PassKind::xp;
+        ps.compress = v != 3;
+    } else if (g.stream_nb != 0 && g.stream_nb <= 2048 && (v == 0 || v == 2 || v == 5 || v == 6 || v == 7)) {
+        ps.kind = v != 2 && g.quad ? PassKind::quad : PassKind::stream;
+        // DNA k = 11, 12 by default (cfg3: 38 % of 4^12 slots per group -- no 64 MB dense table per group to write and read back)
+        ps.compress = v == 6 || (v == 0 && g.stream_tbl == 32768u && sigma == 4);
+    }
+    return ps;
+}
+
 struct Plan {
     uint32_t n_mats = 0, sites = 0, sigma = 0, k = 0;
     float eps = 0;
@@ -1049,12 +916,14 @@ struct Plan {
     uint32_t n_groups = 0, nwin = 0, tiles_per_mat = 0, chunks_per_group = 0;
     uint64_t table_size = 0, gpb = 1;  // slots per group table; groups per batch
     uint32_t lead = 0, lead_c = 0;     // key-range call: the k-mers whose first `lead` symbols spell lead_c (table_size = sigma^(k - lead))
+    Geometry geo;
+    Pass pass;
+    const uint32_t* mat_rank = nullptr;   // positions: each matrix's rank inside its group (device)
 };
 
-// slot_bytes: what a group's table costs per slot (0: by the variant the call will take -- 4 B dense, 0.3125 B compressed)
 int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
               const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl, uint32_t lead = 0, uint32_t lead_c = 0,
-              double slot_bytes = 0.0)
+              bool positions = false)
 {
     if (!logp || !mat_group) return fail(ctx, IPKGPU_ERR_INVALID, "null input pointer");
     if (sigma != 4 && sigma != 20) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported alphabet size %u (4 or 20)", sigma);
@@ -1066,6 +935,8 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
     if (n_mats == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no matrices");
     if (sites < k) return fail(ctx, IPKGPU_ERR_INVALID, "alignment has %u sites, fewer than k=%u", sites, k);
     pl.n_mats = n_mats; pl.sites = sites; pl.sigma = sigma; pl.k = k; pl.eps = log_eps;
+    RC_TRY(fill_geometry(ctx, sigma, k, lead, pl.geo));
+    pl.pass = choose_pass(ctx->opt_variant, sigma, lead, positions, pl.geo);
     pl.slot_of.resize(n_mats);
     std::unordered_map<uint32_t, uint32_t> index;
     index.reserve(n_mats);
@@ -1084,21 +955,17 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
     // phylo-k-mers of its windows, 8 bytes each, at the rate calibrated by the context's previous call or its pre-pass; a
     // guess of 256 per window before that) -- against workspace_bytes.  An underestimate is caught later: a batch whose pool
     // does not fit is halved and scored again (IPKGPU_RETRY_SMALLER).
+    // (the exact partition's compressed tables live in place in the pool: occupancy bits, ranks and value addresses only -- T / 8 +
+    //  T / 16 + T / 8 bytes instead of 4 T; with the dense figure 125 groups of k = 14 were scored in two batches and merged)
     pl.nwin = sites - k + 1;
     {
         const double ppw = ctx->pairs_per_window > 0 ? ctx->pairs_per_window : 256.0;
         const double pool_per_group = (double)n_mats / (double)pl.n_groups * (double)pl.nwin * ppw * 8.0 * 1.25;
-        // (the exact partition ends in compressed tables, in place in the pool: occupancy bits, ranks and value addresses only -- T / 8 +
-        //  T / 16 + T / 8 bytes instead of 4 T; with the dense figure 125 groups of k = 14 were scored in two batches and merged)
-        const uint32_t xnb = xp_buckets(sigma, k, lead);
-        const bool no_dense = xnb != 0 && (ctx->opt_variant == 4 || (ctx->opt_variant == 0 && stream_buckets(sigma, k) == 0));
-        if (slot_bytes <= 0.0) slot_bytes = no_dense ? 0.3125 : 4.0;
-        const double per_group = (double)pl.table_size * slot_bytes + pool_per_group;
+        const double per_group = (double)pl.table_size * pl.pass.slot_bytes() + pool_per_group;
         pl.gpb = std::max<uint64_t>(1, (uint64_t)((double)ctx->workspace_bytes / per_group));
     }
     pl.gpb = std::min<uint64_t>(pl.gpb, pl.n_groups);
     while (pl.gpb > 1 && pl.gpb * pl.chunks_per_group > 0x7fffffffull) pl.gpb /= 2;
-    pl.nwin = sites - k + 1;
     pl.tiles_per_mat = (pl.nwin + TW - 1) / TW;
     return IPKGPU_OK;
 }
@@ -1106,7 +973,7 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
 int run_prefix(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev)
 {
     RC_TRY(ensure(ctx, ctx->best, (size_t)pl.n_mats * (pl.sites + 1) * 4));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->small, 0, 64, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->small, 0, SMALL_BYTES, ctx->stream));
     // matrices per workgroup: as few as keep the call to one round of workgroups (the kernel's registers allow 7 per CU; 4 leaves room)
     uint32_t M = 1;
     while (M < 8 && (pl.n_mats + M - 1) / M > (uint32_t)ctx->num_cu * 4) M *= 2;
@@ -1124,11 +991,12 @@ int scan_u32(ipkgpu_ctx* ctx, const uint32_t* in, uint64_t n, uint64_t* out);
 
 // Exact-partition variant of one batch (kernels_score.hpp): count -> scan -> write -> reduce -> big-list windows.
 // ctx->gm holds the batch's group -> matrices CSR; p carries the shared counters and the big-list queue.
-int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t gb, uint32_t nb, ScoreParams& p, uint32_t XNB, bool compress)
+int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t gb, ScoreParams& p)
 {
-    (void)nb;
+    const uint32_t XNB = pl.geo.xp_nb;
+    const bool compress = pl.pass.compress;
     const uint32_t tiles_per_mat = (pl.nwin + XP_TW - 1) / XP_TW;
-    const size_t lds_bytes = xp_lds_bytes(pl.sigma, pl.k, pl.lead);
+    const size_t lds_bytes = pl.geo.xp_lds;
     const uint64_t wg_per_cu = std::max<uint64_t>(1, std::min<uint64_t>(32 / (pl.sigma == 20 ? IPK_XPNW : 11), (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
     const uint64_t slots = (uint64_t)ctx->num_cu * wg_per_cu;
     // four rounds of resident workgroups balance the tail; a unit costs only its NB counters
@@ -1159,11 +1027,22 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     xp.start = nullptr;
     xp.lead_c = pl.lead_c;
 
+    // the count (WRITE = false) or write pass: the main kernel, then the big-list windows (their kernel reads the queue length on the device)
+    auto xp_kernel = [&](bool write) {
+        return with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
+            return write ? launch_xp<S_, K_, true, KK_>(ctx, xp, gb * S) : launch_xp<S_, K_, false, KK_>(ctx, xp, gb * S);
+        });
+    };
+    auto xp_overflow = [&](bool write) {
+        return with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
+            return write ? launch_xp_overflow<S_, K_, true, KK_>(ctx, xp) : launch_xp_overflow<S_, K_, false, KK_>(ctx, xp);
+        });
+    };
     Stopwatch sw(ctx->stream, &ctx->events);
     const int ev_a = sw.mark();
-    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, false, pl.lead));
+    RC_TRY(xp_kernel(false));
     const int ev_a2 = sw.mark();
-    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, false, pl.lead));          // reads the queue length on the device
+    RC_TRY(xp_overflow(false));
     RC_TRY(scan_u32(ctx, xp.cnt, n_units, ctx->gboff.as<uint64_t>()));
     uint64_t total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->gboff.as<uint64_t>() + n_units, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1183,16 +1062,15 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
         const uint64_t n_start = (uint64_t)gb * S * XNB;
         RC_TRY(ensure(ctx, ctx->xstart, n_start * 4));
         hipLaunchKernelGGL(xp_unit_starts_kernel, dim3((uint32_t)((n_start + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->gboff.as<uint64_t>(), XNB, S, stride, n_start, ctx->xstart.as<uint32_t>(),
-                           reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 56));
+                           ctx->gboff.as<uint64_t>(), XNB, S, stride, n_start, ctx->xstart.as<uint32_t>(), small_at(ctx, SMALL_XP_TOO_BIG));
         HIP_TRY(ctx, hipGetLastError());
         xp.start = ctx->xstart.as<uint32_t>();
     }
     sp.pool = ctx->pool.as<uint2>();
     const int ev_c = sw.mark();
-    RC_TRY(dispatch_xp(ctx, pl.sigma, pl.k, xp, gb * S, true, pl.lead));
+    RC_TRY(xp_kernel(true));
     const int ev_d0 = sw.mark();
-    RC_TRY(dispatch_xp_overflow(ctx, pl.sigma, pl.k, xp, true, pl.lead));
+    RC_TRY(xp_overflow(true));
     const int ev_d = sw.mark();
     if (compress) {
         RC_TRY(ensure(ctx, ctx->rank, (size_t)gb * (ctx->mask_words / 2) * 4));
@@ -1201,16 +1079,20 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     } else {
         RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
     }
-    RC_TRY(dispatch_xp_reduce(ctx, pl.sigma, pl.k, (uint32_t)n_gb, stride, pl.table_size, ctx->gboff.as<uint64_t>(),
-                              compress ? nullptr : ctx->table.as<uint32_t>(), compress, pl.lead));
+    uint32_t* const table = compress ? nullptr : ctx->table.as<uint32_t>();
+    RC_TRY(with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
+        const uint64_t* off = ctx->gboff.as<uint64_t>();
+        return compress ? launch_xp_reduce<S_, K_, true, KK_>(ctx, (uint32_t)n_gb, stride, pl.table_size, off, table)
+                        : launch_xp_reduce<S_, K_, false, KK_>(ctx, (uint32_t)n_gb, stride, pl.table_size, off, table);
+    }));
     const int ev_e = sw.mark();
     uint32_t too_big = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&too_big, reinterpret_cast<char*>(ctx->small) + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&too_big, small_at(ctx, SMALL_XP_TOO_BIG), 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (too_big) return fail(ctx, IPKGPU_ERR_INVALID, "a branch group scores 2^32 phylo-k-mers or more in one batch (exact-partition variant: 32-bit offsets inside a group)");
     ctx->mask_valid = true;
     ctx->table_compressed = compress;
-    ctx->comp_nb = XNB; ctx->comp_stride = stride; ctx->comp_tbl = xp_bucket_slots(pl.sigma, pl.k, pl.lead);
+    ctx->comp_nb = XNB; ctx->comp_stride = stride; ctx->comp_tbl = pl.geo.xp_tbl;
     ctx->acc_main_ms += sw.ms(ev_a, ev_a2) + sw.ms(ev_c, ev_d0);
     ctx->acc_count_ms += sw.ms(ev_a, ev_a2); ctx->acc_write_ms += sw.ms(ev_c, ev_d0);
     ctx->acc_reduce_ms += sw.ms(ev_d, ev_e);
@@ -1226,7 +1108,7 @@ int stream_batch_check(ipkgpu_ctx* ctx)
     if (!pd.active) return IPKGPU_OK;
     pd.active = false;
     std::unique_ptr<Stopwatch> sw(pd.sw.release());
-    const uint32_t n_ovf = ctx->h_rb[4], pool_exhausted = ctx->h_rb[9];
+    const uint32_t n_ovf = ctx->h_rb[SMALL_OVF_COUNT / 4], pool_exhausted = ctx->h_rb[SMALL_POOL_OVF / 4];
     if (pool_exhausted) {
         if (pd.cap >= pd.max_chunks) {
             ctx->pool_want_min = 0;
@@ -1237,7 +1119,7 @@ int stream_batch_check(ipkgpu_ctx* ctx)
         return IPKGPU_RETRY_AGAIN;
     }
     ctx->pool_want_min = 0;
-    memcpy(&ctx->emitted_host, ctx->h_rb, 8);
+    memcpy(&ctx->emitted_host, ctx->h_rb + SMALL_EMITTED / 4, 8);
     ctx->emitted_fetched = true;
     // the next call skips the wait after pass 1 if its big-list windows would take the atomic kernel anyway
     ctx->spec_skip_wait = !(n_ovf > 0 && (uint64_t)n_ovf * IPK_OVF_POOL_RATIO >= pd.windows && pd.pool_ovf_ok);
@@ -1246,12 +1128,12 @@ int stream_batch_check(ipkgpu_ctx* ctx)
 }
 
 // Capped big-list capacity (DNA k >= 13, kernels_score.hpp big_capf): a window whose half list exceeds BIG_CAP_ENTRIES raises the
-// flag word at ctx->small + 44.  arm_capped points p.big_ovf at it and clears it (null where nothing is capped); check_capped, after
+// flag word SMALL_BIG_OVF.  arm_capped points p.big_ovf at it and clears it (null where nothing is capped); check_capped, after
 // the batch's scoring kernels, turns a raised flag into the call's error.
 int arm_capped(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, ScoreParams& p)
 {
     const bool capped_lists = sigma == 4 && k >= 13;
-    p.big_ovf = capped_lists ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 44) : nullptr;
+    p.big_ovf = capped_lists ? small_at(ctx, SMALL_BIG_OVF) : nullptr;
     if (capped_lists) HIP_TRY(ctx, hipMemsetAsync(p.big_ovf, 0, 4, ctx->stream));
     return IPKGPU_OK;
 }
@@ -1267,14 +1149,12 @@ int check_capped(ipkgpu_ctx* ctx, uint32_t k, const ScoreParams& p)
     return IPKGPU_OK;
 }
 
-// Scores groups [g0, g0 + gb) into ctx->table ([gb][table_size]); *emitted_out = scored phylo-k-mers of the batch.
+// Scores groups [g0, g0 + gb) into ctx->table ([gb][table_size]) or the compressed table form, by pl.pass.
 // defer: a stream-variant batch may return with its last wait still owed (ctx->pend.active) -- the caller waits on the stream
 // later anyway and then calls score_batch_finish.
-int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t g0, uint32_t gb,
-                     std::vector<uint32_t>& idx_host, bool defer)
+int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t g0, uint32_t gb, bool defer)
 {
     const uint32_t n_mats = pl.n_mats;
-    (void)idx_host;
     // host side of the batch's index arrays, in pinned staging: [mat_list | mat_slot] (2 x n_mats) and the group -> matrices
     // CSR [gb + 1 offsets | matrices]; both uploads leave without a wait
     uint32_t nb = 0;
@@ -1308,6 +1188,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     HIP_TRY(ctx, hipMemcpyAsync(ctx->gm.p, gm, gm_words * 4, hipMemcpyHostToDevice, ctx->stream));
     RC_TRY(upload_staged(ctx));
 
+    const Pass& ps = pl.pass;
     ScoreParams p;
     p.logp = logp_dev;
     p.best = ctx->best.as<float>();
@@ -1316,54 +1197,36 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     p.n_batch_mats = nb; p.sites = pl.sites; p.nwin = pl.nwin; p.tiles_per_mat = pl.tiles_per_mat;
     p.eps = pl.eps;
     p.table = ctx->table.p;
-    p.mat_rank = nullptr;
+    p.mat_rank = pl.mat_rank;
     p.table_size = pl.table_size;
-    p.emitted = reinterpret_cast<unsigned long long*>(ctx->small);
+    p.emitted = small_at<unsigned long long>(ctx, SMALL_EMITTED);
     p.ovf_queue = ctx->ovfq.as<unsigned long long>();
-    p.ovf_count = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 16);
-    p.flags = (uint32_t)(ctx->opt_variant == 99 ? 1 : 0);
+    p.ovf_count = small_at(ctx, SMALL_OVF_COUNT);
+    p.flags = (uint32_t)(!ps.positions && ctx->opt_variant == 99 ? 1 : 0);
     p.mask = nullptr; p.mask_words = 0;
     // capped big-list capacity (DNA k >= 13, kernels_score.hpp big_capf): the flag word, checked at the end of the batch
     RC_TRY(arm_capped(ctx, pl.sigma, pl.k, p));
     ctx->mask_valid = false;
     ctx->table_compressed = false;
-    const uint32_t NBK = stream_buckets(pl.sigma, pl.k);
-    const uint32_t XNB = xp_buckets(pl.sigma, pl.k, pl.lead);
-    // variant 0 = default: stream where its per-wave chunk state fits (all DNA k, AA k <= 5), exact partition for
-    // AA k=6; 1 = global atomics, 2 = stream (diagnostic flags honoured), 3 = exact partition wherever it exists
-    //                 4 = exact partition ending in the compressed table form (the default for AA k=6: no dense tables --
-    //                     64 GB less at cfg4, 40 % fewer bytes moved; 90.5 vs 92.0 ms through dense tables)
-    const bool use_xp = XNB != 0 && (ctx->opt_variant == 3 || ctx->opt_variant == 4 || (ctx->opt_variant == 0 && NBK == 0) || pl.lead != 0);
-    const bool xp_compress = use_xp && ctx->opt_variant != 3;
-    const bool use_stream = !use_xp && NBK != 0 && NBK <= 2048 && (ctx->opt_variant == 0 || ctx->opt_variant == 2 || ctx->opt_variant == 5 ||
-                                                                   ctx->opt_variant == 6 || ctx->opt_variant == 7);
-    // pass 1 of the stream variant: the quad kernel (kernels_quad.hpp) where it exists (DNA k = 8..12), variant 2 forces the
-    // first-generation score_stream_kernel, variant 5 asks for the quad kernel explicitly
-    const bool use_quad = use_stream && ctx->opt_variant != 2 && quad_supported(pl.sigma, pl.k);
+    ctx->comp_own_vals = false;
+    const bool use_stream = ps.kind == PassKind::stream || ps.kind == PassKind::quad;
+    const bool use_quad = ps.kind == PassKind::quad;
     if (!use_stream) {                                     // (the stream variant resets its counters in one launch: small_reset_kernel)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->small, 0, 8, ctx->stream));            // per-batch scored-k-mer counter
+        HIP_TRY(ctx, hipMemsetAsync(p.emitted, 0, 8, ctx->stream));              // per-batch scored-k-mer counter
         HIP_TRY(ctx, hipMemsetAsync(p.ovf_count, 0, 4, ctx->stream));
     }
-    // The chunk-fed reduce ends in the compressed table form (occupancy bits + rank + the non-empty slots' score codes, comp_table.hpp)
-    // where the scored k-mers fill the key space sparsely: DNA k = 11, 12 (cfg3: 38 % of 4^12 slots per group -- no 64 MB dense table
-    // per group to write and read back); variant 6 forces it for any stream (sigma, k), variant 7 forces dense tables.  The big-list
-    // windows then always go through the pool (the atomic kernel needs dense tables), which bounds the field widths of their queue.
-    const bool pool_ovf_ok = gb < (1u << 22) && n_mats < (1u << 21) && pl.nwin < (1u << 21);
-    bool s_compress = use_stream && pool_ovf_ok && ctx->opt_variant != 7 && ctx->opt_variant != 2 &&
-                      (ctx->opt_variant == 6 || (ctx->opt_variant == 0 && stream_tbl_value(pl.sigma, pl.k) == 32768u && pl.sigma == 4));
-    ctx->comp_own_vals = false;
-    const uint32_t SNW = use_quad ? quad_waves(pl.sigma, pl.k) : stream_waves(pl.sigma, pl.k);
-    const uint32_t STW = use_quad ? quad_tile(pl.sigma, pl.k) : stream_tile(pl.sigma, pl.k);
-    const uint32_t s_tiles_per_mat = (pl.nwin + STW - 1) / STW;
-    if (!use_stream && !xp_compress) {                     // (the stream variant decides its table form below, once the pair rate is known)
-        RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
+    if (ps.kind == PassKind::tiles) {
+        const size_t table_bytes = (size_t)gb * pl.table_size * (ps.positions ? 8 : 4);   // (positions: 8-byte (score, position) entries)
+        RC_TRY(ensure(ctx, ctx->table, table_bytes));
         p.table = ctx->table.p;
-    }
-    if (!use_stream && !use_xp) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->table.p, 0, (size_t)gb * pl.table_size * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->table.p, 0, table_bytes, ctx->stream));
         Stopwatch sw(ctx->stream, &ctx->events);
         const int a = sw.mark();
-        RC_TRY(dispatch_score(ctx, pl.sigma, pl.k, p));
+        RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
+            if (ps.positions) return launch_both<S_, K_, true>(ctx, p);
+            if constexpr (S_ == 4 && K_ > 12) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k (%u/%u)", pl.sigma, pl.k);
+            else return launch_both<S_, K_, false>(ctx, p);
+        }));
         const int b = sw.mark();
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         ctx->acc_main_ms += sw.ms(a, b);
@@ -1371,15 +1234,37 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         return check_capped(ctx, pl.k, p);
     }
 
-    // ---- stream variant: pass 1 (append pairs) -> chunk index -> pass 2 (LDS reduce) -> big-list windows
+    // ---- stream variant and exact partition
     // occupancy bits of the tables: written by the LDS reduce pass, kept current by the big-list kernel, read by km_count
     ctx->mask_words = 2 * ((pl.table_size + 63) / 64);
     RC_TRY(ensure(ctx, ctx->mask, (size_t)gb * ctx->mask_words * 4));
     p.mask = ctx->mask.as<uint32_t>(); p.mask_words = ctx->mask_words;
-    if (use_xp) {
-        const int rc = score_batch_xp(ctx, pl, logp_dev, gb, nb, p, XNB, xp_compress);
+    if (ps.kind == PassKind::xp) {
+        if (!ps.compress) {
+            RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
+            p.table = ctx->table.p;
+        }
+        const int rc = score_batch_xp(ctx, pl, logp_dev, gb, p);
         return rc ? rc : check_capped(ctx, pl.k, p);
     }
+
+    // ---- stream variant: pass 1 (append pairs) -> chunk index -> pass 2 (LDS reduce) -> big-list windows
+    // The chunk-fed reduce ends in the compressed table form (occupancy bits + rank + the non-empty slots' score codes, comp_table.hpp)
+    // where the scored k-mers fill the key space sparsely (ps.compress, and below by the pair rate).  The big-list windows then always
+    // go through the pool (the atomic kernel needs dense tables), which bounds the field widths of their queue.
+    const bool pool_ovf_ok = gb < (1u << 22) && n_mats < (1u << 21) && pl.nwin < (1u << 21);
+    bool s_compress = pool_ovf_ok && ps.compress;
+    const uint32_t NBK = pl.geo.stream_nb, TBL = pl.geo.stream_tbl;
+    const uint32_t SNW = use_quad ? pl.geo.quad_nw : pl.geo.stream_nw;
+    const uint32_t STW = use_quad ? pl.geo.quad_tw : pl.geo.stream_tw;
+    const uint32_t s_tiles_per_mat = (pl.nwin + STW - 1) / STW;
+    // pass 1: the quad kernel (kernels_quad.hpp) or score_stream_kernel; count_only: the quad kernel's count-only form
+    auto pass1 = [&](const StreamParams& sp, uint32_t n_wg, bool count_only) {
+        return with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
+            if (!use_quad) return launch_stream_pass1<S_, K_>(ctx, sp, n_wg);
+            return count_only ? launch_quad_pass1<S_, K_, true>(ctx, sp, n_wg) : launch_quad_pass1<S_, K_, false>(ctx, sp, n_wg);
+        });
+    };
 
     // Segments (workgroups) per group.  More workgroups balance the tail of the persistent kernel, but every
     // wavefront keeps one open chunk per key bucket, so workgroups x waves x buckets must stay well below
@@ -1411,36 +1296,32 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         ss.pool = nullptr; ss.pool_cap = 0; ss.pool_next = nullptr; ss.desc = nullptr; ss.pool_ovf = nullptr; ss.pre_chunks = 0;
         ss.emitted = p.emitted; ss.ovf_queue = p.ovf_queue; ss.ovf_count = p.ovf_count; ss.mat_slot = p.mat_slot;
         ss.flags = 2u;
-        if (use_quad) RC_TRY(dispatch_quad_pass1(ctx, pl.sigma, pl.k, ss, n_s * ss.S, true));
-        else RC_TRY(dispatch_stream_pass1(ctx, pl.sigma, pl.k, ss, n_s * ss.S));
+        RC_TRY(pass1(ss, n_s * ss.S, true));
         unsigned long long se = 0; uint32_t so = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&se, p.emitted, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(&so, p.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const uint64_t s_windows = (uint64_t)slist.size() * pl.nwin;
         // windows that went to the big-list queue were not counted: assume they carry CAP^2 / 4 pairs each (generous)
-        const double cap_pairs = 0.25 * (double)fast_cap_value(pl.sigma, pl.k) * (double)fast_cap_value(pl.sigma, pl.k);
+        const double cap_pairs = 0.25 * (double)pl.geo.fast_cap * (double)pl.geo.fast_cap;
         if (s_windows) ctx->pairs_per_window = std::max(1.0, ((double)se + (double)so * cap_pairs) / (double)s_windows * 1.15);
     }
     const double ppw_est = ctx->pairs_per_window > 0 ? ctx->pairs_per_window : 256.0;
     // ... and wherever the groups are small next to the key space: short alignments (cfg5's D652-like shape: 2 x 1391 windows x 133 pairs
     // per group against 4^10 slots, a third of them ever touched) leave dense tables mostly empty, and the reduce would write and the
     // key-major writer read 4 MB per group for 1.4 MB of scores
-    if (!s_compress && use_stream && pool_ovf_ok && ctx->opt_variant == 0 && pl.table_size >= (1u << 16) &&
+    if (!s_compress && pool_ovf_ok && ctx->opt_variant == 0 && pl.table_size >= (1u << 16) &&
         (double)windows * ppw_est < 0.5 * (double)gb * (double)pl.table_size)
         s_compress = true;
     if (!s_compress) {
         RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
         p.table = ctx->table.p;
     }
-    const size_t lds_bytes = use_quad ? quad_lds_bytes(pl.sigma, pl.k) : stream_lds_bytes(pl.sigma, pl.k);
+    const size_t lds_bytes = use_quad ? pl.geo.quad_lds : pl.geo.stream_lds;
     const uint64_t wg_per_cu = std::max<uint64_t>(1, std::min<uint64_t>(32 / SNW, (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
     const uint64_t slots = (uint64_t)ctx->num_cu * wg_per_cu;
-    const uint32_t CH = chunk_pairs_rt(stream_tbl_value(pl.sigma, pl.k));      // pairs per chunk of this (sigma, k)
+    const uint32_t CH = chunk_pairs_rt(TBL);      // pairs per chunk of this (sigma, k)
     const uint64_t expected_chunks = (uint64_t)((double)windows * ppw_est / CH);
-#ifndef IPK_OVF_POOL_RATIO
-#define IPK_OVF_POOL_RATIO 500
-#endif
 #ifndef IPK_WG_CHUNKS2
 #define IPK_WG_CHUNKS2 2      // a wavefront should fill at least IPK_WG_CHUNKS2 / 2 chunks per bucket (4: +3.5 % at a 125-group share of cfg2)
 #endif
@@ -1490,8 +1371,8 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         RC_TRY(ensure(ctx, ctx->gbcnt, 2 * n_gb * 4));             // [chunks per (group, bucket) | scatter cursors]: one fill for both
         uint32_t* const d_gbcur = ctx->gbcnt.as<uint32_t>() + n_gb;
         RC_TRY(ensure(ctx, ctx->gboff, (n_gb + 1) * 8));
-        uint32_t* d_pool_next = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 32);
-        uint32_t* d_pool_ovf = d_pool_next + 1;
+        uint32_t* d_pool_next = small_at(ctx, SMALL_POOL_NEXT);
+        uint32_t* d_pool_ovf = small_at(ctx, SMALL_POOL_OVF);
         // (row-per-lane quad kernel: the wavefronts' first chunks are handed out by position, the counter starts behind them)
         // (the candidate-per-lane kernel stores through 32-bit offsets from a base chunk, at first the wavefront's own pre-assigned
         //  chunks; in a pool beyond 4 GiB the first chunk it DRAWS lies outside that window and the wavefront rebases once -- by then
@@ -1506,7 +1387,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
             RC_TRY(ensure(ctx, ctx->tile_next, (size_t)gb * 4));
             d_tile_next = ctx->tile_next.as<uint32_t>();
         }
-        hipLaunchKernelGGL(small_reset_kernel, dim3((std::max<uint32_t>(gb, 14) + 255) / 256), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(small_reset_kernel, dim3((std::max<uint32_t>(gb, SMALL_XP_TOO_BIG / 4) + 255) / 256), dim3(256), 0, ctx->stream,
                            reinterpret_cast<uint32_t*>(ctx->small), pre_chunks, d_tile_next, gb, S);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemsetAsync(ctx->desc.p, 0, cap * 8, ctx->stream));   // ids drawn but never opened stay empty
@@ -1525,8 +1406,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         std::unique_ptr<Stopwatch> sw_own(new Stopwatch(ctx->stream, &ctx->events));
         Stopwatch& sw = *sw_own;
         const int ev_a = sw.mark();
-        if (use_quad) RC_TRY(dispatch_quad_pass1(ctx, pl.sigma, pl.k, sp, n_wg));
-        else RC_TRY(dispatch_stream_pass1(ctx, pl.sigma, pl.k, sp, n_wg));
+        RC_TRY(pass1(sp, n_wg, false));
         const int ev_b = sw.mark();
         // windows whose half lists overflowed the fast path: big-list kernel.  With the queue sorted by group it
         // appends to the same pool (LDS max-reduce in pass 2); otherwise (field widths exceeded) it falls back to
@@ -1541,9 +1421,9 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         uint32_t n_ovf = 0;
         uint32_t h[2] = {0, 0};
         if (!spec) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, 64, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, SMALL_BYTES, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            n_ovf = ctx->h_rb[4]; h[0] = ctx->h_rb[8]; h[1] = ctx->h_rb[9];
+            n_ovf = ctx->h_rb[SMALL_OVF_COUNT / 4]; h[0] = ctx->h_rb[SMALL_POOL_NEXT / 4]; h[1] = ctx->h_rb[SMALL_POOL_OVF / 4];
         }
         // a handful of big-list windows (< 0.2 % of the batch) are cheaper through the atomic kernel after pass 2 than
         // through sort + pool kernel; flat posteriors put a large share of the pairs there and need the pool
@@ -1563,13 +1443,13 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
             StreamParams so = sp;
             so.ovf_queue = ctx->tmp_b.as<unsigned long long>();
             // with the quad kernel the pool's pairs are counted from the chunk descriptors: the big-list kernel's own count goes nowhere
-            if (use_quad) so.emitted = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ctx->small) + 48);
-            RC_TRY(dispatch_stream_overflow(ctx, pl.sigma, pl.k, so));
+            if (use_quad) so.emitted = small_at<unsigned long long>(ctx, SMALL_OVF_EMITTED);
+            RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) { return launch_stream_overflow<S_, K_>(ctx, so); }));
         }
         if (ovf_in_pool) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, 64, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, SMALL_BYTES, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            h[0] = ctx->h_rb[8]; h[1] = ctx->h_rb[9];
+            h[0] = ctx->h_rb[SMALL_POOL_NEXT / 4]; h[1] = ctx->h_rb[SMALL_POOL_OVF / 4];
         }
         if (h[1] != 0) {                    // pool exhausted: h[0] chunks were asked for
             if (cap >= max_chunks) {
@@ -1602,9 +1482,8 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         if (s_compress) {
             // where the slices' values go: room for min(pairs, slots) values per (group, bucket), scanned; the buffer itself is sized
             // from what the host knows without another wait -- no more values than pairs, no more pairs than the used chunks hold
-            const uint32_t TBLv = stream_tbl_value(pl.sigma, pl.k);
             hipLaunchKernelGGL(comp_slice_room_kernel, dim3((uint32_t)((n_gb + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->croom.as<uint32_t>(), (uint32_t)n_gb, NBK, pl.table_size, TBLv, ctx->croom.as<uint32_t>() + n_gb);
+                               ctx->croom.as<uint32_t>(), (uint32_t)n_gb, NBK, pl.table_size, TBL, ctx->croom.as<uint32_t>() + n_gb);
             HIP_TRY(ctx, hipGetLastError());
             RC_TRY(ensure(ctx, ctx->coff, (n_gb + 1) * 8));
             RC_TRY(scan_u32(ctx, ctx->croom.as<uint32_t>() + n_gb, n_gb, ctx->coff.as<uint64_t>()));
@@ -1623,17 +1502,20 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
             HIP_TRY(ctx, hipGetLastError());
         }
         const int ev_c = sw.mark();
-        RC_TRY(dispatch_stream_pass2(ctx, pl.sigma, pl.k, (uint32_t)n_gb, pl.table_size, ctx->table.as<uint32_t>(), s_compress));
+        RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
+            return launch_stream_pass2<S_, K_>(ctx, (uint32_t)n_gb, pl.table_size, ctx->table.as<uint32_t>(), s_compress);
+        }));
         const int ev_d = sw.mark();
-        if ((spec || n_ovf > 0) && !ovf_in_pool) RC_TRY(dispatch_overflow(ctx, pl.sigma, pl.k, p));
+        if ((spec || n_ovf > 0) && !ovf_in_pool)
+            RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) { return launch_overflow<S_, K_, false>(ctx, p); }));
         if (s_compress) {
             ctx->table_compressed = true; ctx->comp_own_vals = true;
-            ctx->comp_nb = NBK; ctx->comp_stride = 1; ctx->comp_tbl = stream_tbl_value(pl.sigma, pl.k);
+            ctx->comp_nb = NBK; ctx->comp_stride = 1; ctx->comp_tbl = TBL;
         }
         ctx->mask_valid = true;
         ctx->main_kernel = use_quad ? "score_quad_kernel" : "score_stream_kernel";
         // the batch's counters: copied to pinned words, read at the caller's next wait (defer) or at this one
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, 64, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, SMALL_BYTES, hipMemcpyDeviceToHost, ctx->stream));
         ipkgpu_ctx::Pending& pd = ctx->pend;
         pd.sw.reset(sw_own.release());
         pd.ev_a = ev_a; pd.ev_b = ev_b; pd.ev_c = ev_c; pd.ev_d = ev_d;
@@ -1655,13 +1537,14 @@ int score_batch_finish(ipkgpu_ctx* ctx, const Plan& pl, uint32_t g0, uint32_t gb
     if (ctx->pend.active) RC_TRY(stream_batch_check(ctx));
     unsigned long long e = ctx->emitted_host;
     if (!ctx->emitted_fetched) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, small_at(ctx, SMALL_EMITTED), 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(&e, ctx->h_rb, 8);
     }
     *emitted_acc += e;
     // calibration of the next call's pair pool and workgroup count: PAIRS per window (not chunks -- chunk
-    // counts include every wave's open chunks and would feed back into the workgroup count)
+    // counts include every wave's open chunks and would feed back into the workgroup count).  A positions call calibrates nothing.
+    if (pl.pass.positions) return IPKGPU_OK;
     uint64_t nb = 0;
     for (uint32_t i = 0; i < pl.n_mats; ++i) nb += (pl.slot_of[i] >= g0 && pl.slot_of[i] < g0 + gb);
     if (nb) ctx->pairs_per_window = (double)e / ((double)nb * pl.nwin);
@@ -1669,12 +1552,11 @@ int score_batch_finish(ipkgpu_ctx* ctx, const Plan& pl, uint32_t g0, uint32_t gb
 }
 
 // defer: the caller waits on the stream later anyway; if ctx->pend.active on return, it owes score_batch_finish after that wait
-int score_batch(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t g0, uint32_t gb,
-                std::vector<uint32_t>& idx_host, uint64_t* emitted_acc, bool defer = false)
+int score_batch(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint32_t g0, uint32_t gb, uint64_t* emitted_acc, bool defer = false)
 {
     ctx->emitted_fetched = false;
     ctx->pend.active = false; ctx->pend.sw.reset();
-    RC_TRY(score_batch_impl(ctx, pl, logp_dev, g0, gb, idx_host, defer));
+    RC_TRY(score_batch_impl(ctx, pl, logp_dev, g0, gb, defer));
     if (ctx->pend.active) return IPKGPU_OK;
     return score_batch_finish(ctx, pl, g0, gb, emitted_acc);
 }
@@ -1743,22 +1625,28 @@ int scan_u32(ipkgpu_ctx* ctx, const uint32_t* in, uint64_t n, uint64_t* out)
     return IPKGPU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
 // ---- group-major output ------------------------------------------------------------------------------
-int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
-                               uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
-                               ipkgpu_result** out)
+// The group-major call over device matrices; positions: the KEEP_POSITIONS variant, whose tables hold
+// 8-byte (score, position) entries and whose result carries each entry's position too.
+int group_major(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites, uint32_t sigma, const uint32_t* mat_group,
+                uint32_t k, float log_eps, bool positions, ipkgpu_result** out)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     Plan pl;
-    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl));
+    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl, 0, 0, positions));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t n_groups = pl.n_groups, cpg = pl.chunks_per_group;
+    if (positions) {
+        if ((uint64_t)n_mats * pl.nwin >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many windows per group for the position code");
+        // rank of every matrix inside its group = processing order of explore_group (:641)
+        std::vector<uint32_t> rank(n_mats), seen(n_groups, 0);
+        for (uint32_t i = 0; i < n_mats; ++i) rank[i] = seen[pl.slot_of[i]]++;
+        RC_TRY(ensure(ctx, ctx->branch, (size_t)n_mats * 4));
+        HIP_TRY(ctx, hipMemcpy(ctx->branch.p, rank.data(), (size_t)n_mats * 4, hipMemcpyHostToDevice));
+        pl.mat_rank = ctx->branch.as<uint32_t>();
+    }
 
     ipkgpu_result* res = new (std::nothrow) ipkgpu_result();
     if (!res) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
@@ -1766,6 +1654,9 @@ int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t 
     res->group_ids = pl.group_ids;
     res->offsets.assign((size_t)n_groups + 1, 0);
     struct Guard { ipkgpu_result* r; ~Guard() { if (r) ipkgpu_result_free(r); } } guard{res};
+    // the result's arrays, 4 bytes per entry: keys, scores and, with positions, positions
+    void** const arrays[3] = {(void**)&res->d_keys, (void**)&res->d_scores, (void**)&res->d_positions};
+    const int n_arrays = positions ? 3 : 2;
 
     RC_TRY(ensure(ctx, ctx->counts, (size_t)(pl.gpb * cpg) * 4));
     RC_TRY(ensure(ctx, ctx->offsets, (size_t)(pl.gpb * cpg + 1) * 8));
@@ -1777,13 +1668,12 @@ int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t 
     RC_TRY(run_prefix(ctx, pl, logp_dev));
     const int t_pre = sw.mark();
     std::vector<std::pair<int, int>> ev_score, ev_compact;
-    std::vector<uint32_t> idx_host;
     uint64_t total_entries = 0;
     uint32_t gpb_now = (uint32_t)pl.gpb, gb = 0;
     for (uint32_t g0 = 0; g0 < n_groups; g0 += gb) {
         gb = std::min<uint32_t>(gpb_now, n_groups - g0);
         const int s0 = sw.mark();
-        const int rcb = score_batch(ctx, pl, logp_dev, g0, gb, idx_host, &res->emitted);
+        const int rcb = score_batch(ctx, pl, logp_dev, g0, gb, &res->emitted);
         if (rcb == IPKGPU_RETRY_SMALLER) { gpb_now = std::max<uint32_t>(1, gb / 2); gb = 0; continue; }   // the batch again, half as many groups
         if (rcb) return rcb;
         const int s1 = sw.mark();
@@ -1799,7 +1689,10 @@ int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t 
                 hipLaunchKernelGGL(add_base_kernel, dim3((n_chunks + 1 + 255) / 256), dim3(256), 0, ctx->stream,
                                    ctx->offsets.as<uint64_t>(), (uint64_t)n_chunks + 1, total_entries);
         } else {
-            if (ctx->mask_valid)
+            if (positions)
+                hipLaunchKernelGGL(count_chunks64_kernel, dim3(n_chunks), dim3(256), 0, ctx->stream,
+                                   ctx->table.as<unsigned long long>(), pl.table_size, cpg, ctx->counts.as<uint32_t>());
+            else if (ctx->mask_valid)
                 hipLaunchKernelGGL(count_chunks_mask_kernel, dim3(n_chunks), dim3(256), 0, ctx->stream,
                                    ctx->mask.as<uint32_t>(), ctx->mask_words, cpg, ctx->counts.as<uint32_t>());
             else
@@ -1819,33 +1712,31 @@ int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t 
         if (new_total > res->cap) {
             // grow the output (exact when the last batch is reached; doubling across batches)
             const size_t new_cap = (g0 + gb >= n_groups) ? (size_t)new_total : (size_t)std::max<uint64_t>(new_total, 2 * res->cap);
-            uint32_t* nk = nullptr; float* ns = nullptr;
-            HIP_TRY(ctx, ctx_alloc(ctx, (void**)&nk, std::max<size_t>(new_cap, 1) * 4));
-            hipError_t e2 = ctx_alloc(ctx, (void**)&ns, std::max<size_t>(new_cap, 1) * 4);
-            if (e2 != hipSuccess) { ctx_release(ctx, nk); HIP_TRY(ctx, e2); }
+            void* grown[3] = {nullptr, nullptr, nullptr};
+            for (int a = 0; a < n_arrays; ++a) {
+                const hipError_t e = ctx_alloc(ctx, &grown[a], std::max<size_t>(new_cap, 1) * 4);
+                if (e != hipSuccess) { for (int b = 0; b < a; ++b) ctx_release(ctx, grown[b]); HIP_TRY(ctx, e); }
+            }
             if (total_entries) {
-                (void)hipMemcpyAsync(nk, res->d_keys, total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipMemcpyAsync(ns, res->d_scores, total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
+                for (int a = 0; a < n_arrays; ++a)
+                    (void)hipMemcpyAsync(grown[a], *arrays[a], total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
                 (void)hipStreamSynchronize(ctx->stream);
             }
-            ctx_release(ctx, res->d_keys);
-            ctx_release(ctx, res->d_scores);
-            res->d_keys = nk; res->d_scores = ns; res->cap = new_cap;
+            for (int a = 0; a < n_arrays; ++a) { ctx_release(ctx, *arrays[a]); *arrays[a] = grown[a]; }
+            res->cap = new_cap;
         }
-        if (ctx->table_compressed) {
-            const CompTable ct = comp_table(ctx);
-            if (sigma == 4)
-                hipLaunchKernelGGL(write_group_c_kernel<4>, dim3(n_chunks), dim3(256), 0, ctx->stream, ct,
+        auto write = [&](auto S_) {
+            if (ctx->table_compressed)
+                hipLaunchKernelGGL(write_group_c_kernel<S_>, dim3(n_chunks), dim3(256), 0, ctx->stream, comp_table(ctx),
                                    pl.table_size, (int)k, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores);
+            else if (positions)
+                hipLaunchKernelGGL(write_chunks_pos_kernel<S_>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<unsigned long long>(),
+                                   pl.table_size, cpg, (int)k, pl.nwin, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores, res->d_positions);
             else
-                hipLaunchKernelGGL(write_group_c_kernel<20>, dim3(n_chunks), dim3(256), 0, ctx->stream, ct,
-                                   pl.table_size, (int)k, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores);
-        } else if (sigma == 4)
-            hipLaunchKernelGGL(write_chunks_kernel<4>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<uint32_t>(),
-                               pl.table_size, cpg, (int)k, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores);
-        else
-            hipLaunchKernelGGL(write_chunks_kernel<20>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<uint32_t>(),
-                               pl.table_size, cpg, (int)k, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores);
+                hipLaunchKernelGGL(write_chunks_kernel<S_>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<uint32_t>(),
+                                   pl.table_size, cpg, (int)k, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores);
+        };
+        if (sigma == 4) write(int_c<4>{}); else write(int_c<20>{});
         HIP_TRY(ctx, hipGetLastError());
         ev_compact.push_back({s1, sw.mark()});
         total_entries = new_total;
@@ -1862,8 +1753,9 @@ int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t 
     return IPKGPU_OK;
 }
 
-int ipkgpu_score_groups(ipkgpu_ctx* ctx, const float* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
-                        const uint32_t* mat_group, uint32_t k, float log_eps, ipkgpu_result** out)
+// The group-major call over host matrices: copied to the device for the call
+int group_major_host(ipkgpu_ctx* ctx, const float* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma, const uint32_t* mat_group,
+                     uint32_t k, float log_eps, bool positions, ipkgpu_result** out)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
@@ -1877,127 +1769,32 @@ int ipkgpu_score_groups(ipkgpu_ctx* ctx, const float* logp, uint32_t n_mats, uin
     HIP_TRY(ctx, hipMalloc((void**)&d, std::max<size_t>(bytes, 4)));
     hipError_t e = hipMemcpy(d, logp, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(ctx, e); }
-    const int rc = ipkgpu_score_groups_device(ctx, d, n_mats, sites, sigma, mat_group, k, log_eps, out);
+    const int rc = group_major(ctx, d, n_mats, sites, sigma, mat_group, k, log_eps, positions, out);
     (void)hipFree(d);
     return rc;
 }
 
-// ---- KEEP_POSITIONS variant -------------------------------------------
+}  // namespace
+
+extern "C" {
+
+int ipkgpu_score_groups_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                               uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                               ipkgpu_result** out)
+{
+    return group_major(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, false, out);
+}
+
+int ipkgpu_score_groups(ipkgpu_ctx* ctx, const float* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
+                        const uint32_t* mat_group, uint32_t k, float log_eps, ipkgpu_result** out)
+{
+    return group_major_host(ctx, logp, n_mats, sites, sigma, mat_group, k, log_eps, false, out);
+}
+
 int ipkgpu_score_groups_positions(ipkgpu_ctx* ctx, const float* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
                                   const uint32_t* mat_group, uint32_t k, float log_eps, ipkgpu_result** out)
 {
-    if (!ctx) return IPKGPU_ERR_INVALID;
-    if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
-    *out = nullptr;
-    Plan pl;
-    // dense 8-byte table entries (score, position) whatever the (sigma, k): priced as such against workspace_bytes
-    RC_TRY(make_plan(ctx, logp, n_mats, sites, sigma, mat_group, k, log_eps, pl, 0, 0, 8.0));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((uint64_t)n_mats * pl.nwin >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many windows per group for the position code");
-    const uint32_t n_groups = pl.n_groups, cpg = pl.chunks_per_group;
-
-    ipkgpu_result* res = new (std::nothrow) ipkgpu_result();
-    if (!res) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
-    res->ctx = ctx;
-    res->group_ids = pl.group_ids;
-    res->offsets.assign((size_t)n_groups + 1, 0);
-    struct Guard { ipkgpu_result* r; ~Guard() { if (r) ipkgpu_result_free(r); } } guard{res};
-
-    // host matrices in; rank of every matrix inside its group = processing order of explore_group (:641)
-    const size_t bytes = (size_t)n_mats * sites * sigma * 4;
-    float* d_logp = nullptr;
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&d_logp, std::max<size_t>(bytes, 4)));
-    struct LGuard { ipkgpu_ctx* c; void* p; ~LGuard() { ctx_release(c, p); } } lguard{ctx, d_logp};
-    HIP_TRY(ctx, hipMemcpy(d_logp, logp, bytes, hipMemcpyHostToDevice));
-    std::vector<uint32_t> rank(n_mats), seen(n_groups, 0);
-    for (uint32_t i = 0; i < n_mats; ++i) rank[i] = seen[pl.slot_of[i]]++;
-    RC_TRY(ensure(ctx, ctx->branch, (size_t)n_mats * 4));
-    HIP_TRY(ctx, hipMemcpy(ctx->branch.p, rank.data(), (size_t)n_mats * 4, hipMemcpyHostToDevice));
-
-    RC_TRY(ensure(ctx, ctx->counts, (size_t)(pl.gpb * cpg) * 4));
-    RC_TRY(ensure(ctx, ctx->offsets, (size_t)(pl.gpb * cpg + 1) * 8));
-    RC_TRY(ensure(ctx, ctx->goff, (size_t)(pl.gpb + 1) * 8));
-    ctx->acc_main_ms = ctx->acc_reduce_ms = ctx->acc_count_ms = ctx->acc_write_ms = ctx->acc_km_ms = 0;
-    Stopwatch sw(ctx->stream, &ctx->events);
-    const int t_begin = sw.mark();
-    RC_TRY(run_prefix(ctx, pl, d_logp));
-    std::vector<uint32_t> idx_host((size_t)n_mats * 2);
-    uint64_t total_entries = 0;
-    for (uint32_t g0 = 0; g0 < n_groups; g0 += (uint32_t)pl.gpb) {
-        const uint32_t gb = std::min<uint32_t>((uint32_t)pl.gpb, n_groups - g0);
-        uint32_t nb = 0;
-        for (uint32_t i = 0; i < n_mats; ++i) {
-            idx_host[n_mats + i] = 0;
-            if (pl.slot_of[i] >= g0 && pl.slot_of[i] < g0 + gb) { idx_host[nb++] = i; idx_host[n_mats + i] = pl.slot_of[i] - g0; }
-        }
-        RC_TRY(ensure(ctx, ctx->idx, (size_t)n_mats * 8));
-        RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 8));
-        RC_TRY(ensure(ctx, ctx->ovfq, (size_t)nb * pl.nwin * 8));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->idx.p, idx_host.data(), (size_t)n_mats * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ScoreParams p;
-        p.logp = d_logp; p.best = ctx->best.as<float>();
-        p.mat_list = ctx->idx.as<uint32_t>(); p.mat_slot = ctx->idx.as<uint32_t>() + n_mats;
-        p.n_batch_mats = nb; p.sites = sites; p.nwin = pl.nwin; p.tiles_per_mat = pl.tiles_per_mat; p.eps = log_eps;
-        p.table = ctx->table.p; p.table_size = pl.table_size; p.mat_rank = ctx->branch.as<uint32_t>();
-        p.mask = nullptr; p.mask_words = 0;
-        p.emitted = reinterpret_cast<unsigned long long*>(ctx->small);
-        p.ovf_queue = ctx->ovfq.as<unsigned long long>();
-        p.ovf_count = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 16);
-        p.flags = 0;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->table.p, 0, (size_t)gb * pl.table_size * 8, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(p.ovf_count, 0, 4, ctx->stream));
-        RC_TRY(arm_capped(ctx, sigma, k, p));
-        RC_TRY(dispatch_score_pos(ctx, sigma, k, p));
-        RC_TRY(check_capped(ctx, k, p));
-        res->score_launches += 1;
-        const uint32_t n_chunks = gb * cpg;
-        hipLaunchKernelGGL(count_chunks64_kernel, dim3(n_chunks), dim3(256), 0, ctx->stream,
-                           ctx->table.as<unsigned long long>(), pl.table_size, cpg, ctx->counts.as<uint32_t>());
-        hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, ctx->stream,
-                           ctx->counts.as<uint32_t>(), (uint64_t)n_chunks, total_entries, ctx->offsets.as<uint64_t>());
-        hipLaunchKernelGGL(gather_offsets_kernel, dim3((gb + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                           ctx->offsets.as<uint64_t>(), cpg, gb + 1, ctx->goff.as<uint64_t>());
-        HIP_TRY(ctx, hipGetLastError());
-        std::vector<uint64_t> goff((size_t)gb + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(goff.data(), ctx->goff.p, ((size_t)gb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (uint32_t g = 0; g <= gb; ++g) res->offsets[g0 + g] = goff[g];
-        const uint64_t new_total = goff[gb];
-        if (new_total > res->cap) {
-            const size_t new_cap = (g0 + gb >= n_groups) ? (size_t)new_total : (size_t)std::max<uint64_t>(new_total, 2 * res->cap);
-            uint32_t *nk = nullptr, *np = nullptr; float* ns = nullptr;
-            HIP_TRY(ctx, ctx_alloc(ctx, (void**)&nk, std::max<size_t>(new_cap, 1) * 4));
-            hipError_t e2 = ctx_alloc(ctx, (void**)&ns, std::max<size_t>(new_cap, 1) * 4);
-            hipError_t e3 = e2 == hipSuccess ? ctx_alloc(ctx, (void**)&np, std::max<size_t>(new_cap, 1) * 4) : e2;
-            if (e3 != hipSuccess) { ctx_release(ctx, nk); ctx_release(ctx, ns); HIP_TRY(ctx, e3); }
-            if (total_entries) {
-                (void)hipMemcpyAsync(nk, res->d_keys, total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipMemcpyAsync(ns, res->d_scores, total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipMemcpyAsync(np, res->d_positions, total_entries * 4, hipMemcpyDeviceToDevice, ctx->stream);
-                (void)hipStreamSynchronize(ctx->stream);
-            }
-            ctx_release(ctx, res->d_keys); ctx_release(ctx, res->d_scores); ctx_release(ctx, res->d_positions);
-            res->d_keys = nk; res->d_scores = ns; res->d_positions = np; res->cap = new_cap;
-        }
-        if (sigma == 4)
-            hipLaunchKernelGGL(write_chunks_pos_kernel<4>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<unsigned long long>(),
-                               pl.table_size, cpg, (int)k, pl.nwin, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores, res->d_positions);
-        else
-            hipLaunchKernelGGL(write_chunks_pos_kernel<20>, dim3(n_chunks), dim3(256), 0, ctx->stream, ctx->table.as<unsigned long long>(),
-                               pl.table_size, cpg, (int)k, pl.nwin, ctx->offsets.as<uint64_t>(), res->d_keys, res->d_scores, res->d_positions);
-        HIP_TRY(ctx, hipGetLastError());
-        total_entries = new_total;
-    }
-    const int t_end = sw.mark();
-    unsigned long long emitted = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&emitted, ctx->small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    res->emitted = emitted;
-    res->t_total = sw.ms(t_begin, t_end);
-    guard.r = nullptr;
-    *out = res;
-    return IPKGPU_OK;
+    return group_major_host(ctx, logp, n_mats, sites, sigma, mat_group, k, log_eps, true, out);
 }
 
 const uint32_t* ipkgpu_result_positions(ipkgpu_result* r)
@@ -2191,7 +1988,6 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
     const int t_pre = sw.mark();
     std::vector<std::pair<int, int>> ev_score, ev_compact, ev_km;
     std::pair<int, int> ev_keys{-1, -1};
-    std::vector<uint32_t> idx_host;
 
     struct Batch { uint32_t* counts = nullptr; uint2* entries = nullptr; std::vector<uint64_t> owner_off; };
     std::vector<Batch> batches;
@@ -2205,7 +2001,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         const int s0 = sw.mark();
         // (defer: a stream-variant batch returns without a wait of its own; what it owes -- the pool's state, the scored count --
         //  is settled at this loop's one wait, score_batch_finish below)
-        const int rcb = score_batch(ctx, pl, logp_dev, g0, gb, idx_host, &parts->emitted, true);
+        const int rcb = score_batch(ctx, pl, logp_dev, g0, gb, &parts->emitted, true);
         if (rcb == IPKGPU_RETRY_SMALLER) { gpb_now = std::max<uint32_t>(1, gb / 2); gb = 0; continue; }   // the batch again, half as many groups
         if (rcb) return rcb;
         const int s1 = sw.mark();
@@ -2845,7 +2641,7 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
         RC_TRY(ensure(ctx, ctx->tmp_a, n * 4));
         RC_TRY(ensure(ctx, ctx->tmp_b, (n + 1) * 8));
         const auto t0 = std::chrono::steady_clock::now();
-        uint32_t* d_big = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->small) + 60);
+        uint32_t* d_big = small_at(ctx, SMALL_REC_BIG);
         HIP_TRY(ctx, hipMemsetAsync(d_big, 0, 4, ctx->stream));
         hipLaunchKernelGGL(db_record_sizes_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, db->d_order, db->d_key_off, n,
                            ctx->tmp_a.as<uint32_t>(), d_big);

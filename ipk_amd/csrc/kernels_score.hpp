@@ -844,13 +844,24 @@ __global__ __launch_bounds__(256) void chunk_scatter_kernel(const unsigned long 
     }
 }
 
-// The per-batch counters of ctx->small in one launch (they were five 4-us fills): scored k-mers @0, big-list queue length @16,
-// chunk ids drawn @32 (starting behind the chunks handed out by position), pool-exhausted flag @36, spare counter @48.
+// The context's 64-byte counter block (ipkgpu_ctx::small): byte offsets of its fields.
+constexpr uint32_t SMALL_EMITTED = 0;        // u64 scored phylo-k-mers of the batch
+constexpr uint32_t SMALL_OVF_COUNT = 16;     // u32 big-list queue length
+constexpr uint32_t SMALL_POOL_NEXT = 32;     // u32 chunk ids drawn from the pair pool
+constexpr uint32_t SMALL_POOL_OVF = 36;      // u32 the pair pool ran out
+constexpr uint32_t SMALL_BIG_OVF = 44;       // u32 a half list exceeded the capped big-list capacity (DNA k >= 13)
+constexpr uint32_t SMALL_OVF_EMITTED = 48;   // u64 the pooled big-list kernel's own count (discarded with the quad kernel)
+constexpr uint32_t SMALL_XP_TOO_BIG = 56;    // u32 a group's exact partition reached 2^32 pairs
+constexpr uint32_t SMALL_REC_BIG = 60;       // u32 a database record of 2^28 entries or more (ipkgpu_db_write)
+constexpr uint32_t SMALL_BYTES = 64;
+
+// The per-batch counters of ctx->small in one launch (they were five 4-us fills): every field before SMALL_XP_TOO_BIG is cleared,
+// the chunk counter starts behind the chunks handed out by position.
 __global__ void small_reset_kernel(uint32_t* __restrict__ small, uint32_t pre_chunks, uint32_t* __restrict__ tile_next, uint32_t n_groups,
                                    uint32_t first_tile)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 14) small[i] = i == 8 ? pre_chunks : 0u;
+    if (i < SMALL_XP_TOO_BIG / 4) small[i] = i == SMALL_POOL_NEXT / 4 ? pre_chunks : 0u;
     if (tile_next && i < n_groups) tile_next[i] = first_tile;   // (the quad kernel's per-group tile counters ride along: tiles [0, S) go by position)
 }
 
