@@ -230,6 +230,22 @@ int ipkgpu_score_groups_keymajor_device(ipkgpu_ctx* ctx, const float* logp_dev, 
 int ipkgpu_score_groups_keyrange_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
                                         uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
                                         uint32_t lead_symbols, uint32_t lead_class, ipkgpu_parts** out);
+/*
+ * Positioned database (the reference's ipk-aa-pos flavour, db_builder.cpp:655-662,687-689; branch_group.cpp:73-86): as
+ * ipkgpu_score_groups_keymajor_device, every entry also carrying the start of the window that produced its score -- among windows of
+ * equal score bits the one explore_group processes first (the group's matrices in input order, then ascending start).  Keys, key
+ * order, entry order and score bits equal those of ipkgpu_score_groups_keymajor_device on the same input; the position rides
+ * along through ONE scoring pass (the exact partition with compressed tables: sequence numbers beside the pairs, an LDS reduce on
+ * (score, first window), the key-major writer run over the position values as well).
+ * n_owners must be 1 (the exchange does not carry positions); supported where the exact partition exists: amino acids k = 2..6,
+ * DNA k = 4..14; a group's matrices x windows must stay below 2^32.  Anything else: IPKGPU_ERR_INVALID with a message.
+ * ipkgpu_db_from_parts moves the positions into the database with the entries; ipkgpu_db_write then writes the positioned file.
+ */
+int ipkgpu_score_groups_keymajor_positions_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                                  uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                                  uint32_t n_owners, ipkgpu_parts** out);
+/* u32 [entries] window starts aligned entry for entry with ipkgpu_parts_entries_device; NULL for parts of the other calls */
+const uint32_t* ipkgpu_parts_positions_device(const ipkgpu_parts* p);
 /* lead_class * sigma^(k - lead_symbols) for key-range parts; 0 for other parts */
 uint64_t ipkgpu_parts_key_base(const ipkgpu_parts* p);
 uint32_t ipkgpu_parts_num_owners(const ipkgpu_parts* p);
@@ -297,6 +313,10 @@ const uint32_t* ipkgpu_db_entries(ipkgpu_db* d);
 const uint32_t* ipkgpu_db_keys_device(const ipkgpu_db* d);
 const uint64_t* ipkgpu_db_key_offsets_device(const ipkgpu_db* d);
 const void* ipkgpu_db_entries_device(const ipkgpu_db* d);
+/* window starts u32[num_entries] of a database built from positioned parts, aligned with the entries (host copy on first use);
+ * NULL for databases without positions */
+const uint32_t* ipkgpu_db_positions(ipkgpu_db* d);
+const uint32_t* ipkgpu_db_positions_device(const ipkgpu_db* d);
 double ipkgpu_db_time_ms(const ipkgpu_db* d);
 void ipkgpu_db_free(ipkgpu_db* d);
 
@@ -397,7 +417,10 @@ typedef struct ipkgpu_db_header {
 /* save_header + save_phylo_kmer for every k-mer in filter order (db_builder.cpp:297-306,323-327), streamed from device
  * memory: the records are packed on the GPU in pieces, copied through pinned buffers and written while the next piece is
  * being packed.  Needs ipkgpu_db_filter_mif0 first.  Byte layout: ipk_amd/csrc/ipk_format.hpp -- i2l and Boost are
- * un-vendored, so the layout is a reconstruction (Boost binary_oarchive primitives) and NOT pinned against a real .ipk. */
+ * un-vendored, so the layout is a reconstruction (Boost binary_oarchive primitives) and NOT pinned against a real .ipk.
+ * A database that has positions (ipkgpu_db_positions_device != NULL) is written as the positioned file, byte for byte what
+ * ipkgpu_db_write_host_positions writes from its host arrays; refused with that function's messages, before the file is created,
+ * when a window position exceeds 65535 or when IPKGPU_IPK_PROTOCOL_VERSION=0. */
 int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* header, const char* path, uint64_t* bytes_written);
 /* The same serialiser over host arrays (merged shards of several GPUs, or a filter computed on the host):
  * entries u32 [n][2] = (branch, score bits); order = positions of the k-mers in output order (NULL: as stored). */

@@ -59,8 +59,8 @@ def ipk():
 @click.option("--ar-config", type=click.Path(), help="(ignored)")
 @click.option("--keep-positions", is_flag=True,
               help="(ipk-aa-pos; amino acids, one GPU) every database entry carries the window position of its kept score "
-                   "(db_builder.cpp:655-662,687-689): positions are scored per branch (ipkgpu_score_groups_positions) and joined with "
-                   "the key-major database on the host; the entry layout (branch, score, u16 position) is a guess like the rest of the file")
+                   "(db_builder.cpp:655-662,687-689): the position rides along through the one scoring pass on the device "
+                   "(ipkgpu_score_groups_keymajor_positions_device); the entry layout (branch, score, u16 position) is a guess like the rest of the file")
 @click.option("--uncompressed", is_flag=True, help="(ignored, as in the reference)")
 @click.option("--threads", type=int, default=0,
               help="host threads of the probability loader [0 = every core this process may run on, divided among the ranks of a node; the reference's --threads only "
@@ -85,8 +85,8 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     if keep_positions and states == "nucl":
         raise click.UsageError("--keep-positions is not supported for DNA.")              # ipk.py:281-282
     if keep_positions and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("--keep-positions: the positioned database is assembled by ONE process (positions are scored per branch, "
-                               "ipkgpu_score_groups_positions, and joined with the key-major database on the host); run without torchrun")
+        raise click.UsageError("--keep-positions: the positioned database is built by ONE process (the k-mer-keyed exchange between ranks "
+                               "does not carry positions yet); run without torchrun")
     if merge_branches:
         raise click.UsageError("--merge-branches is not supported (the reference only guards it, main.cpp:31-37)")
     from ipk_amd import tree as T
@@ -195,7 +195,8 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     if world > 1:
         import torch
         mats = torch.from_numpy(np.ascontiguousarray(mats)).cuda()
-    db, parts = distributed.build_db_shard(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, dist, world, rank)
+    db, parts = distributed.build_db_shard(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, dist, world, rank,
+                                           positions=keep_positions)
     t_score = time.time() - t0
     # MIF0's N = _original_tree.get_node_count() (db_builder.cpp:261); without a tree: groups = the non-root nodes (:524-553)
     n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
@@ -205,33 +206,19 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
         db.filter_mif0(eng, n_nodes, ipk_amd.score_threshold(omega, sigma, k))
     t_filter = time.time() - t0
     t0 = time.time()
-    if keep_positions:
-        # KEEP_POSITIONS (branch_group.cpp:73-86): the kept score's window position.  The database above has the same scores (the position
-        # only rides along with the max); the per-branch positioned result is joined to it entry by entry on the host.
-        res = eng.score_groups_positions(mats.cpu().numpy() if hasattr(mats, "cpu") else mats, np.array(branches, dtype=np.uint32), k, log_eps)
-        keys_db, off_db = db.keys(), db.key_offsets().astype(np.int64)
+    if keep_positions and filter_ != "mif0":
+        # KEEP_POSITIONS (branch_group.cpp:73-86) with the random filter: the positioned database's host arrays (the position of every
+        # entry came out of the scoring pass with its score), the filter drawn as below
+        keys_db = db.keys()
         br_db, sc_db = db.entries()
-        entry_key = np.repeat(keys_db, np.diff(off_db))
-        pos_db = np.empty(len(br_db), dtype=np.uint32)
-        rk, rs, rp = res.keys(), res.scores(), res.positions()
-        for gi, gid in enumerate(res.group_ids.tolist()):
-            a, b = int(res.offsets[gi]), int(res.offsets[gi + 1])
-            sel = np.flatnonzero(br_db == gid)
-            idx = np.searchsorted(rk[a:b], entry_key[sel])
-            if len(sel) != b - a or not np.array_equal(rk[a:b][idx], entry_key[sel]) or \
-               not np.array_equal(rs[a:b][idx].view(np.uint32), sc_db[sel].view(np.uint32)):
-                raise click.ClickException("positioned scoring and the database disagree (internal error)")
-            pos_db[sel] = rp[a:b][idx]
-        res.free()
-        if filter_ == "mif0":
-            fv_p, order_p = db.filter_values(), db.filter_order()
-        else:
-            fv_p = (dbfile.splitmix_unit(keys_db) if db.num_keys else np.zeros(0)).astype(np.float32)
-            order_p = np.argsort(dbfile.filter_sort_code(fv_p, keys_db), kind="stable")
+        pos_db = db.positions()
+        fv_p = (dbfile.splitmix_unit(keys_db) if db.num_keys else np.zeros(0)).astype(np.float32)
+        order_p = np.argsort(dbfile.filter_sort_code(fv_p, keys_db), kind="stable")
 
         def write_shard(file):
             dbfile.write_db_positions(file, seq_name, tree_index, newick, k, omega, keys_db, db.key_offsets(), br_db, sc_db, pos_db, fv_p, order_p)
     elif filter_ == "mif0":
+        # (--keep-positions: `db` carries positions, and the device writer packs the positioned records)
         # records packed on the device in filter order and streamed to the file (ipkgpu_db_write): the database itself on one
         # GPU, this rank's shard on several (a shard's header carries only its totals)
         def write_shard(file):

@@ -84,6 +84,14 @@ __device__ __forceinline__ void store8_lanes(const void* uniform_base, uint32_t 
     asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx2 %0, %1, %2 offset:%4\n\ts_mov_b64 exec, -1"
                  : : "v"(byte_off), "v"(data), "s"(uniform_base), "s"(mask), "n"(IMM) : "memory");
 }
+// the 4-byte form (the sequence numbers that travel beside the pairs of a positioned call)
+template <int IMM = 0>
+__device__ __forceinline__ void store4_lanes(const void* uniform_base, uint32_t byte_off, uint32_t x, uint64_t mask)
+{
+    IPK_ASSERT_FULL_EXEC();
+    asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dword %0, %1, %2 offset:%4\n\ts_mov_b64 exec, -1"
+                 : : "v"(byte_off), "v"(x), "s"(uniform_base), "s"(mask), "n"(IMM) : "memory");
+}
 
 __device__ __forceinline__ uint32_t mbcnt(uint64_t mask)
 {

@@ -63,6 +63,8 @@ constexpr uint64_t ENTRY_BYTES = 8;                          // branch, score
 constexpr uint64_t ENTRY_POS_BYTES = 10;                     // branch, score, position (u16: ASSUMPTION)
 
 IPKFMT_HD inline uint64_t record_bytes(uint64_t n_entries) { return RECORD_HEAD_BYTES + ENTRY_BYTES * n_entries; }
+IPKFMT_HD inline uint64_t record_bytes_positions(uint64_t n_entries) { return RECORD_HEAD_BYTES + ENTRY_POS_BYTES * n_entries; }
+constexpr uint32_t POSITION_MAX = 0xFFFFu;                   // the largest window position the entry's field holds
 
 // the four 32-bit words of a record's head
 IPKFMT_HD inline void record_head(uint32_t key, uint32_t fv_bits, uint64_t n_entries, uint32_t (&w)[4])

@@ -118,6 +118,8 @@ struct ipkgpu_ctx {
     // compressed table form (exact-partition variant on sparse key spaces; comp_table.hpp): no dense ctx->table
     bool table_compressed = false;
     DevBuf rank, vaddr, ucnt, qpack, xstart, pcounts;
+    DevBuf seq, pvals, pvaddr, mrank, cursnap;   // positioned key-major call: sequence numbers beside the pool, the winners' window starts in slot order,
+                                        // their per-block addresses (beside vaddr), the matrices' ranks in their groups, the writer's cursors before a pass
     DevBuf cvals, coff, croom;          // compressed output of the chunk-fed reduce: values, their offsets per (group, bucket), room
     bool comp_own_vals = false;         // the compressed values live in cvals / coff (chunked pool) instead of in place in the pool
     std::vector<uint32_t> h_branch;     // host copy of the last call's branch ids (source of an asynchronous upload)
@@ -179,6 +181,7 @@ struct ipkgpu_parts {
     uint64_t slots = 0;                       // padded key slots per owner = ceil(sigma^k / n_owners)
     uint32_t* d_counts = nullptr;             // [n_owners][slots]
     uint2* d_entries = nullptr;               // owner-major, key-major, group order: (branch, score bits)
+    uint32_t* d_positions = nullptr;          // positioned call: the window start of every entry, aligned with d_entries
     std::vector<uint64_t> owner_off;          // [n_owners + 1] entry offsets
     uint64_t emitted = 0;
     // one owner, one batch: the database's key list (the non-empty slots and their entry offsets) is built inside the scoring
@@ -196,6 +199,9 @@ struct ipkgpu_db {
     uint32_t* d_keys = nullptr;               // [n_keys] packed codes, ascending
     uint64_t* d_key_off = nullptr;            // [n_keys + 1]
     uint2* d_entries = nullptr;               // [n_entries] (branch, score bits)
+    uint32_t* d_positions = nullptr;          // [n_entries] window starts (databases of a positioned call), else null
+    std::vector<uint32_t> h_positions;
+    bool h_pos_ok = false;
     std::vector<uint32_t> h_keys;
     std::vector<uint64_t> h_key_off;
     std::vector<uint32_t> h_entries;          // [n_entries][2]
@@ -405,7 +411,7 @@ void ipkgpu_destroy(ipkgpu_ctx* ctx)
                       &ctx->branch, &ctx->scan_sums, &ctx->scan_boff, &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c,
                       &ctx->pool, &ctx->desc, &ctx->gbcnt, &ctx->gboff, &ctx->gbcur, &ctx->clist, &ctx->gm, &ctx->tile_next, &ctx->mask,
                       &ctx->rank, &ctx->vaddr, &ctx->ucnt, &ctx->qpack, &ctx->xstart, &ctx->pcounts, &ctx->ptrs,
-                      &ctx->cvals, &ctx->coff, &ctx->croom};
+                      &ctx->cvals, &ctx->coff, &ctx->croom, &ctx->seq, &ctx->pvals, &ctx->pvaddr, &ctx->mrank, &ctx->cursnap};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : ctx->free_blocks) (void)hipFree(b.first);
     ipkgpu_comm_release(ctx);
@@ -714,7 +720,7 @@ template <int SIGMA, int K, int KK = K> size_t xp_lds() {
         return TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8 + (size_t)NB * 4;
     }
 }
-template <int SIGMA, int K, bool WRITE, int KK = K>
+template <int SIGMA, int K, bool WRITE, int KK = K, bool POS = false>
 int launch_xp(ipkgpu_ctx* ctx, const XpParams& xp, uint32_t n_wg)
 {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
@@ -725,7 +731,7 @@ int launch_xp(ipkgpu_ctx* ctx, const XpParams& xp, uint32_t n_wg)
         constexpr size_t lds = TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8 + (size_t)NB * 4;
         static_assert(lds <= 160 * 1024, "exact-partition LDS budget");
         static_assert((TileGeo<SIGMA, K, XP_TW>::HEAD_BYTES + (size_t)xp_nw<SIGMA, K>() * stream_wave_scratch<SIGMA, K, CAP>() * 8) % 8 == 0, "cursor alignment");
-        auto kern = score_xp_kernel<SIGMA, K, CAP, XP_TW, xp_nw<SIGMA, K>(), TBL, WRITE, KK>;
+        auto kern = score_xp_kernel<SIGMA, K, CAP, XP_TW, xp_nw<SIGMA, K>(), TBL, WRITE, KK, POS>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(n_wg), dim3(xp_nw<SIGMA, K>() * 64), lds, ctx->stream, xp);
@@ -733,7 +739,7 @@ int launch_xp(ipkgpu_ctx* ctx, const XpParams& xp, uint32_t n_wg)
         return IPKGPU_OK;
     }
 }
-template <int SIGMA, int K, bool WRITE, int KK = K>
+template <int SIGMA, int K, bool WRITE, int KK = K, bool POS = false>
 int launch_xp_overflow(ipkgpu_ctx* ctx, const XpParams& xp)
 {
     constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
@@ -743,7 +749,7 @@ int launch_xp_overflow(ipkgpu_ctx* ctx, const XpParams& xp)
     } else {
         constexpr size_t lds = TileGeo<SIGMA, K, 1>::HEAD_BYTES + (size_t)wave_scratch_entries<SIGMA, K, big_capf<SIGMA, K>()>() * 8;
         static_assert(lds + 64 <= 160 * 1024, "big-list (exact partition) LDS budget");
-        auto kern = score_overflow_xp_kernel<SIGMA, K, TBL, WRITE, KK>;
+        auto kern = score_overflow_xp_kernel<SIGMA, K, TBL, WRITE, KK, POS>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(32 / OVF_NW, (160 * 1024) / (lds + 64)));
@@ -767,6 +773,27 @@ int launch_xp_reduce(ipkgpu_ctx* ctx, uint32_t n_gb, uint32_t S, uint64_t T, con
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(n_gb), dim3(NT), lds, ctx->stream, ctx->pool.as<uint2>(), off, S, NB, T, table,
                            ctx->mask.as<uint32_t>(), ctx->mask_words, ctx->rank.as<uint32_t>(), ctx->vaddr.as<uint64_t>(), ctx->ucnt.as<uint32_t>());
+        HIP_TRY(ctx, hipGetLastError());
+        return IPKGPU_OK;
+    }
+}
+// the positions pass of a positioned call (reduce_ranges_pos_kernel), ahead of launch_xp_reduce<.., true>
+template <int SIGMA, int K>
+int launch_xp_reduce_pos(ipkgpu_ctx* ctx, uint32_t n_gb, uint32_t S, uint64_t T, const uint64_t* off, uint32_t nwin)
+{
+    constexpr uint32_t TBL = xp_tbl<SIGMA, K>();
+    if constexpr (TBL == 0) { (void)n_gb; (void)S; (void)T; (void)off; (void)nwin; return fail(ctx, IPKGPU_ERR_INVALID, "exact-partition variant unsupported"); }
+    else {
+        constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
+        static_assert(NB == 1 || TBL % 64 == 0, "a 64-slot block must not straddle two buckets");
+        constexpr int NT = pos_sub_slots<TBL>() <= 4096 ? 256 : 1024;
+        constexpr size_t lds = (size_t)pos_sub_blocks<TBL>() * 64 * 8 + (pos_sub_blocks<TBL>() + 1) * 4;
+        static_assert(lds <= 160 * 1024, "positions reduce LDS budget");
+        auto kern = reduce_ranges_pos_kernel<TBL, NT>;
+        if (lds > 64 * 1024)
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(n_gb), dim3(NT), lds, ctx->stream, ctx->pool.as<uint2>(), ctx->seq.as<uint32_t>(), off, S, NB, T, nwin,
+                           ctx->mask_words, ctx->pvals.as<uint32_t>(), ctx->pvaddr.as<uint64_t>());
         HIP_TRY(ctx, hipGetLastError());
         return IPKGPU_OK;
     }
@@ -882,20 +909,23 @@ constexpr int IPKGPU_RETRY_AGAIN = 101;                  // internal: the same b
 // the first-generation score_stream_kernel (diagnostic flags honoured), 3 = exact partition wherever it exists, with dense tables,
 // 4 = exact partition ending in the compressed table form (the default for AA k=6: no dense tables -- 64 GB less at cfg4, 40 % fewer
 // bytes moved; 90.5 vs 92.0 ms through dense tables), 5 = stream variant with the quad kernel, 6 / 7 = stream variant with compressed /
-// dense tables.  Key-range calls take the exact partition, positions the tiles kernel.
+// dense tables.  Key-range calls take the exact partition, the group-major positions call the tiles kernel, the positioned key-major call the
+// exact partition with compressed tables and a sequence number beside every pair (Pass::seq).
 enum class PassKind { tiles, stream, quad, xp };
 struct Pass {
     PassKind kind = PassKind::tiles;
     bool positions = false;            // tiles kernel with 8-byte (score, position) table entries
     bool compress = false;             // compressed tables: the exact partition's, or where the stream variant must take them
+    bool seq = false;                  // positioned key-major call: the exact partition's pairs carry their windows' sequence numbers
     double slot_bytes() const { return positions ? 8.0 : kind == PassKind::xp && compress ? 0.3125 : 4.0; }
 };
 
-Pass choose_pass(int64_t variant, uint32_t sigma, uint32_t lead, bool positions, const Geometry& g)
+Pass choose_pass(int64_t variant, uint32_t sigma, uint32_t lead, bool positions, bool km_positions, const Geometry& g)
 {
     Pass ps;
     ps.positions = positions;
     if (positions) return ps;
+    if (km_positions) { ps.kind = PassKind::xp; ps.compress = true; ps.seq = true; return ps; }   // (make_plan: the exact partition exists)
     const int64_t v = variant;
     if (g.xp_nb != 0 && (v == 3 || v == 4 || (v == 0 && g.stream_nb == 0) || lead != 0)) {
         ps.kind = PassKind::xp;
@@ -923,7 +953,7 @@ struct Plan {
 
 int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites, uint32_t sigma,
               const uint32_t* mat_group, uint32_t k, float log_eps, Plan& pl, uint32_t lead = 0, uint32_t lead_c = 0,
-              bool positions = false)
+              bool positions = false, bool km_positions = false)
 {
     if (!logp || !mat_group) return fail(ctx, IPKGPU_ERR_INVALID, "null input pointer");
     if (sigma != 4 && sigma != 20) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported alphabet size %u (4 or 20)", sigma);
@@ -936,7 +966,10 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
     if (sites < k) return fail(ctx, IPKGPU_ERR_INVALID, "alignment has %u sites, fewer than k=%u", sites, k);
     pl.n_mats = n_mats; pl.sites = sites; pl.sigma = sigma; pl.k = k; pl.eps = log_eps;
     RC_TRY(fill_geometry(ctx, sigma, k, lead, pl.geo));
-    pl.pass = choose_pass(ctx->opt_variant, sigma, lead, positions, pl.geo);
+    if (km_positions && (lead != 0 || pl.geo.xp_nb == 0))
+        return fail(ctx, IPKGPU_ERR_INVALID, "no positioned database for sigma=%u k=%u: the call takes the exact partition, which needs more than 64 keys "
+                                             "and no key-range pass", sigma, k);
+    pl.pass = choose_pass(ctx->opt_variant, sigma, lead, positions, km_positions, pl.geo);
     pl.slot_of.resize(n_mats);
     std::unordered_map<uint32_t, uint32_t> index;
     index.reserve(n_mats);
@@ -960,7 +993,8 @@ int make_plan(ipkgpu_ctx* ctx, const void* logp, uint32_t n_mats, uint32_t sites
     pl.nwin = sites - k + 1;
     {
         const double ppw = ctx->pairs_per_window > 0 ? ctx->pairs_per_window : 256.0;
-        const double pool_per_group = (double)n_mats / (double)pl.n_groups * (double)pl.nwin * ppw * 8.0 * 1.25;
+        // (a positioned call: 4 bytes of sequence number and 4 of position value beside the pair's 8)
+        const double pool_per_group = (double)n_mats / (double)pl.n_groups * (double)pl.nwin * ppw * (pl.pass.seq ? 16.0 : 8.0) * 1.25;
         const double per_group = (double)pl.table_size * pl.pass.slot_bytes() + pool_per_group;
         pl.gpb = std::max<uint64_t>(1, (uint64_t)((double)ctx->workspace_bytes / per_group));
     }
@@ -1028,12 +1062,17 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     xp.lead_c = pl.lead_c;
 
     // the count (WRITE = false) or write pass: the main kernel, then the big-list windows (their kernel reads the queue length on the device)
+    const bool seq = pl.pass.seq;                            // (positioned calls: lead == 0, compressed tables -- choose_pass)
     auto xp_kernel = [&](bool write) {
+        if (write && seq)
+            return with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) { return launch_xp<S_, K_, true, K_, true>(ctx, xp, gb * S); });
         return with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
             return write ? launch_xp<S_, K_, true, KK_>(ctx, xp, gb * S) : launch_xp<S_, K_, false, KK_>(ctx, xp, gb * S);
         });
     };
     auto xp_overflow = [&](bool write) {
+        if (write && seq)
+            return with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) { return launch_xp_overflow<S_, K_, true, K_, true>(ctx, xp); });
         return with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
             return write ? launch_xp_overflow<S_, K_, true, KK_>(ctx, xp) : launch_xp_overflow<S_, K_, false, KK_>(ctx, xp);
         });
@@ -1051,7 +1090,10 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         const bool over_limit = ctx->opt_pool_limit > 0 && total * 8 > (uint64_t)ctx->opt_pool_limit;
-        if (over_limit || (total * 8 > ctx->pool.cap && total * 8 > free_b + ctx->pool.cap)) {
+        const uint64_t side = seq ? total * 8 + 512 : 0;          // sequence numbers and position values, 4 bytes per pair each
+        const uint64_t side_have = seq ? ctx->seq.cap + ctx->pvals.cap : 0;
+        if (over_limit || (total * 8 > ctx->pool.cap && total * 8 > free_b + ctx->pool.cap) ||
+            (side > side_have && total * 8 + side > free_b + ctx->pool.cap + side_have)) {
             if (gb > 1) return IPKGPU_RETRY_SMALLER;
             return fail(ctx, IPKGPU_ERR_NOMEM, "the pair pool of ONE branch group (%llu pairs) does not fit device memory", (unsigned long long)total);
         }
@@ -1067,6 +1109,11 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
         xp.start = ctx->xstart.as<uint32_t>();
     }
     sp.pool = ctx->pool.as<uint2>();
+    if (seq) {
+        RC_TRY(ensure(ctx, ctx->seq, std::max<uint64_t>(total, 1) * 4 + 256));
+        RC_TRY(ensure(ctx, ctx->pvals, std::max<uint64_t>(total, 1) * 4 + 256));      // (+256: as the pool -- the writer reads past a row's values)
+        xp.seq = ctx->seq.as<uint32_t>(); xp.mat_rank = pl.mat_rank;
+    }
     const int ev_c = sw.mark();
     RC_TRY(xp_kernel(true));
     const int ev_d0 = sw.mark();
@@ -1080,6 +1127,12 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
         RC_TRY(ensure(ctx, ctx->table, (size_t)gb * pl.table_size * 4));
     }
     uint32_t* const table = compress ? nullptr : ctx->table.as<uint32_t>();
+    if (seq) {                                               // the winners' positions, while the pairs are still there
+        RC_TRY(ensure(ctx, ctx->pvaddr, (size_t)gb * (ctx->mask_words / 2) * 8));
+        RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
+            return launch_xp_reduce_pos<S_, K_>(ctx, (uint32_t)n_gb, stride, pl.table_size, ctx->gboff.as<uint64_t>(), pl.nwin);
+        }));
+    }
     RC_TRY(with_xp_shape(ctx, pl.sigma, pl.k, pl.lead, [&](auto S_, auto K_, auto KK_) {
         const uint64_t* off = ctx->gboff.as<uint64_t>();
         return compress ? launch_xp_reduce<S_, K_, true, KK_>(ctx, (uint32_t)n_gb, stride, pl.table_size, off, table)
@@ -1937,12 +1990,14 @@ int merge_sources(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, u
 
 // The key-major call; lead > 0: the key-range pass of the k-mers whose first `lead` symbols spell lead_c (one owner)
 int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites, uint32_t sigma, const uint32_t* mat_group,
-                  uint32_t k, float log_eps, uint32_t n_owners, uint32_t lead, uint32_t lead_c, ipkgpu_parts** out)
+                  uint32_t k, float log_eps, uint32_t n_owners, uint32_t lead, uint32_t lead_c, ipkgpu_parts** out, bool positions = false)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (n_owners == 0) return fail(ctx, IPKGPU_ERR_INVALID, "n_owners must be >= 1");
+    if (positions && n_owners != 1) return fail(ctx, IPKGPU_ERR_INVALID, "a positioned database is built for one owner (n_owners = %u): the exchange does not carry positions", n_owners);
+    if (positions && n_mats == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no matrices");
     const uint64_t key_base = lead ? (uint64_t)lead_c * ipow(sigma, (int)(k - lead)) : 0;
     if (n_mats == 0) {
         // a rank without branch groups (more ranks than groups): empty parts, so that it still takes part in the exchange
@@ -1963,8 +2018,18 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         return IPKGPU_OK;
     }
     Plan pl;
-    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl, lead, lead_c));
+    RC_TRY(make_plan(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, pl, lead, lead_c, false, positions));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (positions) {
+        // rank of every matrix inside its group = processing order of explore_group (:641); a window's sequence number rank * nwin + start in 32 bits
+        std::vector<uint32_t> rank(n_mats), seen(pl.n_groups, 0);
+        for (uint32_t i = 0; i < n_mats; ++i) rank[i] = seen[pl.slot_of[i]]++;
+        const uint32_t most = *std::max_element(seen.begin(), seen.end());
+        if ((uint64_t)most * pl.nwin >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many windows per group for the position code (%u matrices x %u windows)", most, pl.nwin);
+        RC_TRY(ensure(ctx, ctx->mrank, (size_t)n_mats * 4));
+        HIP_TRY(ctx, hipMemcpy(ctx->mrank.p, rank.data(), (size_t)n_mats * 4, hipMemcpyHostToDevice));
+        pl.mat_rank = ctx->mrank.as<uint32_t>();
+    }
     const uint64_t T = pl.table_size;
     const uint32_t P = n_owners;
     const uint64_t slots = (T + P - 1) / P;
@@ -1989,9 +2054,10 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
     std::vector<std::pair<int, int>> ev_score, ev_compact, ev_km;
     std::pair<int, int> ev_keys{-1, -1};
 
-    struct Batch { uint32_t* counts = nullptr; uint2* entries = nullptr; std::vector<uint64_t> owner_off; };
+    // (pentries, positioned calls: the writer's second pass, over the position values -- (branch, window start) records aligned with entries)
+    struct Batch { uint32_t* counts = nullptr; uint2* entries = nullptr; uint2* pentries = nullptr; std::vector<uint64_t> owner_off; };
     std::vector<Batch> batches;
-    auto free_batches = [&]() { for (auto& b : batches) { ctx_release(ctx, b.counts); ctx_release(ctx, b.entries); } batches.clear(); };
+    auto free_batches = [&]() { for (auto& b : batches) { ctx_release(ctx, b.counts); ctx_release(ctx, b.entries); ctx_release(ctx, b.pentries); } batches.clear(); };
     struct BGuard { decltype(free_batches)& f; ~BGuard() { f(); } } bguard{free_batches};
 
     const uint64_t n_slots_all = (uint64_t)P * slots;
@@ -2070,7 +2136,12 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         }
 
         // the key-major writer over `cap_e` entries of room
+        // (dst / posv: a positioned call runs it twice from the same cursors -- over the score codes into the entries, then over the position
+        //  values, which stand at the same rank-relative index behind pvaddr, into pentries)
+        uint2* w_dst = nullptr; bool w_posv = false;
+        auto comp_table_w = [&]() { CompTable c = comp_table(ctx); if (w_posv) c.vaddr = ctx->pvaddr.as<uint64_t>(); return c; };
         auto launch_writer = [&](uint64_t cap_e) -> int {
+            uint2* const dst_entries = w_dst ? w_dst : b.entries;
             if (ctx->table_compressed) {
                 uint64_t per_xcd = (((T + 63) / 64) + 7) / 8;
                 // (the writer that walks runs of consecutive key blocks; debug_flags bit 12: one workgroup per key block)
@@ -2080,11 +2151,11 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
                 const bool runs = !(ctx->opt_flags & 4096) && IPK_KMC_RUNS_DEFAULT && (rows_now <= 128 || (ctx->opt_flags & 8192));
                 if (runs && (qpack || fast_c)) per_xcd = (kmc_runs(T, ctx->comp_tbl) + 7) / 8;
                 if (qpack && runs)
-                    KM_LAUNCH(km_write_c_run_kernel, KMC_CAP, comp_table(ctx), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots, b.counts,
-                              qpack, ctx->offsets.as<uint64_t>(), b.entries, cap_e);
+                    KM_LAUNCH(km_write_c_run_kernel, KMC_CAP, comp_table_w(), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots, b.counts,
+                              qpack, ctx->offsets.as<uint64_t>(), dst_entries, cap_e);
                 else if (qpack)
-                    KM_LAUNCH(km_write_c_kernel, KMC_CAP, comp_table(ctx), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots, b.counts,
-                              qpack, ctx->offsets.as<uint64_t>(), b.entries, cap_e);
+                    KM_LAUNCH(km_write_c_kernel, KMC_CAP, comp_table_w(), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots, b.counts,
+                              qpack, ctx->offsets.as<uint64_t>(), dst_entries, cap_e);
                 else if (fast_c) {
                     // more than 256 groups: passes of 256, each with its own counts; the cursors (the scan of the TOTAL counts) advance
                     // from pass to pass, so a key's entries stay in group order
@@ -2099,19 +2170,21 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
                             hipLaunchKernelGGL(km_count_mask_key_kernel, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, ctx->stream,
                                                pmask, ctx->mask_words, T, pg, P, slots, ctx->pcounts.as<uint32_t>(), ctx->qpack.as<uint32_t>());
                         HIP_TRY(ctx, hipGetLastError());
-                        CompTable ctp = comp_table(ctx);
+                        CompTable ctp = comp_table_w();
                         ctp.mask = pmask;
                         ctp.vaddr += (size_t)p0 * (ctx->mask_words / 2);
                         ctp.rank += (size_t)p0 * (ctx->mask_words / 2);
                         if (runs)
                             KM_LAUNCH(km_write_c_run_kernel, KMC_CAP, ctp, T, pg, ctx->branch.as<uint32_t>() + g0 + p0, P, slots, ctx->pcounts.as<uint32_t>(),
-                                      ctx->qpack.as<uint32_t>(), ctx->offsets.as<uint64_t>(), b.entries, cap_e);
+                                      ctx->qpack.as<uint32_t>(), ctx->offsets.as<uint64_t>(), dst_entries, cap_e);
                         else
                             KM_LAUNCH(km_write_c_kernel, KMC_CAP, ctp, T, pg, ctx->branch.as<uint32_t>() + g0 + p0, P, slots, ctx->pcounts.as<uint32_t>(),
-                                      ctx->qpack.as<uint32_t>(), ctx->offsets.as<uint64_t>(), b.entries, cap_e);
+                                      ctx->qpack.as<uint32_t>(), ctx->offsets.as<uint64_t>(), dst_entries, cap_e);
                         HIP_TRY(ctx, hipGetLastError());
                     }
-                } else
+                } else if (positions)
+                    return fail(ctx, IPKGPU_ERR_INVALID, "a positioned database of this many key slots per group would take the generic key-major writer, which carries no positions");
+                else
                     hipLaunchKernelGGL(km_write_c_generic_kernel, dim3((uint32_t)((((T + 63) / 64 + 7) / 8) * 8)), dim3(256), 0, ctx->stream,
                                        comp_table(ctx), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots,
                                        ctx->offsets.as<uint64_t>(), b.entries, cap_e);
@@ -2132,7 +2205,8 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         // BEFORE the host knows the total: the batch's one wait then covers scoring, counting and writing.  A writer that finds
         // less room than the total leaves everything untouched (kernels_keymajor.hpp) and runs again below, after that wait.
         uint64_t cap_e = 0;
-        const bool spec_e = rb_ok && ctx->last_gb > 0 && ctx->last_entries > 0 && !(ctx->opt_flags & 64);
+        // (a positioned call writes after the wait: its two writer passes start from a copy of the cursors)
+        const bool spec_e = rb_ok && ctx->last_gb > 0 && ctx->last_entries > 0 && !(ctx->opt_flags & 64) && !positions;
         int km0 = -1, km1 = -1;
         if (spec_e) {
             const uint64_t est = (uint64_t)((unsigned __int128)ctx->last_entries * gb / ctx->last_gb);
@@ -2157,7 +2231,22 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         if (b.owner_off[P] > cap_e || cap_e == 0) {
             ctx_release(ctx, b.entries); b.entries = nullptr;
             HIP_TRY(ctx, ctx_alloc(ctx, (void**)&b.entries, std::max<uint64_t>(b.owner_off[P], 1) * 8));
-            km0 = sw.mark(); RC_TRY(launch_writer(std::max<uint64_t>(b.owner_off[P], 1))); km1 = sw.mark();
+            const uint64_t n_e = std::max<uint64_t>(b.owner_off[P], 1);
+            km0 = sw.mark();
+            if (positions) {
+                if (!ctx->table_compressed) return fail(ctx, IPKGPU_ERR_INVALID, "internal: a positioned call ended in dense tables");
+                const size_t cur_bytes = (n_slots_all + 1) * 8;
+                RC_TRY(ensure(ctx, ctx->cursnap, cur_bytes));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->cursnap.p, ctx->offsets.p, cur_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                RC_TRY(launch_writer(n_e));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->offsets.p, ctx->cursnap.p, cur_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, ctx_alloc(ctx, (void**)&b.pentries, n_e * 8));
+                w_dst = b.pentries; w_posv = true;
+                RC_TRY(launch_writer(n_e));
+                w_dst = nullptr; w_posv = false;
+            } else
+                RC_TRY(launch_writer(n_e));
+            km1 = sw.mark();
         }
         ctx->last_entries = b.owner_off[P]; ctx->last_gb = gb;
         if (pre_keys) {
@@ -2169,10 +2258,22 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         ev_compact.push_back({s1, km1});
     }
 
+    auto extract_positions = [&](const uint2* src, uint64_t n, uint32_t* dst) -> int {
+        if (!n) return IPKGPU_OK;
+        hipLaunchKernelGGL(extract_positions_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, src, n, dst);
+        HIP_TRY(ctx, hipGetLastError());
+        return IPKGPU_OK;
+    };
     if (batches.size() == 1) {
         parts->d_counts = batches[0].counts; parts->d_entries = batches[0].entries;
         parts->owner_off = batches[0].owner_off;
         batches[0].counts = nullptr; batches[0].entries = nullptr;
+        if (positions) {
+            const int m0 = sw.mark();
+            HIP_TRY(ctx, ctx_alloc(ctx, (void**)&parts->d_positions, std::max<uint64_t>(parts->owner_off[P], 1) * 4));
+            RC_TRY(extract_positions(batches[0].pentries, parts->owner_off[P], parts->d_positions));
+            ev_compact.push_back({m0, sw.mark()});
+        }
     } else {
         // several batches of groups: per owner, merge the batches (sources in batch = group order)
         const int m0 = sw.mark();
@@ -2181,6 +2282,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         uint64_t grand = 0;
         for (auto& b : batches) grand += b.owner_off[P];
         HIP_TRY(ctx, ctx_alloc(ctx, (void**)&parts->d_entries, std::max<uint64_t>(grand, 1) * 8));
+        if (positions) HIP_TRY(ctx, ctx_alloc(ctx, (void**)&parts->d_positions, std::max<uint64_t>(grand, 1) * 4));
         uint64_t done = 0;
         int rc = IPKGPU_OK;
         for (uint32_t o = 0; o < P && rc == IPKGPU_OK; ++o) {
@@ -2192,6 +2294,17 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
             if (rc == IPKGPU_OK) {
                 if (n_total) (void)hipMemcpyAsync(parts->d_entries + done, dst, n_total * 8, hipMemcpyDeviceToDevice, ctx->stream);
                 (void)hipStreamSynchronize(ctx->stream);
+                if (positions) {
+                    // the same merge over the batches' (branch, position) records: the positions follow their entries
+                    std::vector<const uint2*> prow(S);
+                    for (uint32_t s = 0; s < S; ++s) prow[s] = batches[s].pentries + batches[s].owner_off[o];
+                    uint2* pdst = nullptr; uint64_t pn = 0;
+                    rc = merge_sources(ctx, sigma, k, o, P, S, slots, crow, prow, parts->d_counts + (size_t)o * slots, &pdst, &pn, nullptr);
+                    if (rc == IPKGPU_OK && pn != n_total) rc = fail(ctx, IPKGPU_ERR_HIP, "internal: the positions' merge disagrees with the entries'");
+                    if (rc == IPKGPU_OK) rc = extract_positions(pdst, pn, parts->d_positions + done);
+                    (void)hipStreamSynchronize(ctx->stream);
+                    ctx_release(ctx, pdst);
+                }
                 parts->owner_off[o] = done; done += n_total; parts->owner_off[o + 1] = done;
             }
             ctx_release(ctx, dst);
@@ -2239,7 +2352,15 @@ int ipkgpu_score_groups_keyrange_device(ipkgpu_ctx* ctx, const float* logp_dev, 
     return keymajor_impl(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, 1, lead_symbols, lead_class, out);
 }
 
+int ipkgpu_score_groups_keymajor_positions_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                                  uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                                  uint32_t n_owners, ipkgpu_parts** out)
+{
+    return keymajor_impl(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, n_owners, 0, 0, out, true);
+}
+
 uint64_t ipkgpu_parts_key_base(const ipkgpu_parts* p) { return p ? p->key_base : 0; }
+const uint32_t* ipkgpu_parts_positions_device(const ipkgpu_parts* p) { return p ? p->d_positions : nullptr; }
 
 uint32_t ipkgpu_parts_num_owners(const ipkgpu_parts* p) { return p ? p->n_owners : 0; }
 uint64_t ipkgpu_parts_slots(const ipkgpu_parts* p) { return p ? p->slots : 0; }
@@ -2270,6 +2391,7 @@ void ipkgpu_parts_free(ipkgpu_parts* p)
     if (p->ctx) {
         (void)hipSetDevice(p->ctx->device);
         ctx_release(p->ctx, p->d_counts); ctx_release(p->ctx, p->d_entries); ctx_release(p->ctx, p->pre_keys); ctx_release(p->ctx, p->pre_key_off);
+        ctx_release(p->ctx, p->d_positions);
     }
     delete p;
 }
@@ -2361,6 +2483,7 @@ int ipkgpu_db_from_parts(ipkgpu_ctx* ctx, ipkgpu_parts* parts, uint32_t sigma, u
         db->n_entries = parts->owner_off[1];
         db->d_entries = parts->d_entries;      // ownership moves to the database
         parts->d_entries = nullptr;
+        db->d_positions = parts->d_positions; parts->d_positions = nullptr;
         db->t_merge = parts->t_keys;
         guard.r = nullptr;
         *out = db;
@@ -2401,6 +2524,7 @@ int ipkgpu_db_from_parts(ipkgpu_ctx* ctx, ipkgpu_parts* parts, uint32_t sigma, u
     db->n_entries = parts->owner_off[1];
     db->d_entries = parts->d_entries;          // ownership moves to the database
     parts->d_entries = nullptr;
+    db->d_positions = parts->d_positions; parts->d_positions = nullptr;
     db->t_merge = sw.ms(t0, t1);
     guard.r = nullptr;
     *out = db;
@@ -2430,6 +2554,19 @@ static bool db_to_host(ipkgpu_db* d)
 const uint32_t* ipkgpu_db_keys(ipkgpu_db* d) { return d && db_to_host(d) ? d->h_keys.data() : nullptr; }
 const uint64_t* ipkgpu_db_key_offsets(ipkgpu_db* d) { return d && db_to_host(d) ? d->h_key_off.data() : nullptr; }
 const uint32_t* ipkgpu_db_entries(ipkgpu_db* d) { return d && db_to_host(d) ? d->h_entries.data() : nullptr; }
+
+const uint32_t* ipkgpu_db_positions_device(const ipkgpu_db* d) { return d ? d->d_positions : nullptr; }
+const uint32_t* ipkgpu_db_positions(ipkgpu_db* d)
+{
+    if (!d || !d->d_positions) return nullptr;
+    if (!d->h_pos_ok) {
+        (void)hipSetDevice(d->ctx->device);
+        d->h_positions.resize(std::max<uint64_t>(d->n_entries, 1));
+        if (d->n_entries && hipMemcpy(d->h_positions.data(), d->d_positions, d->n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
+        d->h_pos_ok = true;
+    }
+    return d->h_positions.data();
+}
 
 float ipkgpu_score_threshold(float omega, uint32_t sigma, uint32_t k) { return powf(omega / (float)sigma, (float)k); }
 
@@ -2500,6 +2637,7 @@ void ipkgpu_db_free(ipkgpu_db* d)
     if (d->ctx) {
         (void)hipSetDevice(d->ctx->device);
         ctx_release(d->ctx, d->d_keys); ctx_release(d->ctx, d->d_key_off); ctx_release(d->ctx, d->d_entries);
+        ctx_release(d->ctx, d->d_positions);
         ctx_release(d->ctx, d->d_fv64); ctx_release(d->ctx, d->d_fv32); ctx_release(d->ctx, d->d_order);
     }
     delete d;
@@ -2624,6 +2762,23 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
     if (db->n_keys && (!db->d_fv32 || !db->d_order)) return fail(ctx, IPKGPU_ERR_INVALID, "filter values missing: call ipkgpu_db_filter_mif0 first");
     if (db->n_keys >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many k-mers");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // a database with positions is written as the positioned file (ipkgpu_db_write_host_positions' layout and refusals, before the file exists)
+    const bool positioned = db->d_positions != nullptr;
+    if (positioned) {
+        if (ipkfmt::protocol_version() == 0)
+            return fail(ctx, IPKGPU_ERR_INVALID, "a positioned database needs the positions flag: IPKGPU_IPK_PROTOCOL_VERSION must not be 0");
+        if (db->n_entries) {
+            uint32_t* d_far = small_at(ctx, SMALL_REC_BIG);
+            uint32_t h_far = 0;
+            HIP_TRY(ctx, hipMemsetAsync(d_far, 0, 4, ctx->stream));
+            hipLaunchKernelGGL(db_positions_check_kernel, dim3((uint32_t)((db->n_entries + 255) / 256)), dim3(256), 0, ctx->stream, db->d_positions,
+                               db->n_entries, d_far);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(&h_far, d_far, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (h_far) return fail(ctx, IPKGPU_ERR_INVALID, "a window position beyond 65535 does not fit the entry's position field");
+        }
+    }
     const auto t_begin = std::chrono::steady_clock::now();
     double t_dev = 0, t_file = 0;
     auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -2633,7 +2788,7 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
     setvbuf(out.f, nullptr, _IONBF, 0);                              // the pieces are large: no second copy through stdio
     const uint64_t n = db->n_keys;
     const std::vector<uint8_t> head = ipkfmt::file_head(h->sequence_type, h->tree_index_size, h->tree_num_nodes, h->tree_subtree_length, h->newick,
-                                                        h->kmer_size, h->omega, n, db->n_entries);
+                                                        h->kmer_size, h->omega, n, db->n_entries, positioned);
     uint64_t total = head.size();
     { const auto t0 = std::chrono::steady_clock::now(); if (!out.put(head.data(), head.size())) return fail(ctx, IPKGPU_ERR_INVALID, "write failed"); t_file += since(t0); }
     if (n) {
@@ -2644,7 +2799,7 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
         uint32_t* d_big = small_at(ctx, SMALL_REC_BIG);
         HIP_TRY(ctx, hipMemsetAsync(d_big, 0, 4, ctx->stream));
         hipLaunchKernelGGL(db_record_sizes_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, db->d_order, db->d_key_off, n,
-                           ctx->tmp_a.as<uint32_t>(), d_big);
+                           ctx->tmp_a.as<uint32_t>(), d_big, positioned);
         HIP_TRY(ctx, hipGetLastError());
         RC_TRY(scan_u32(ctx, ctx->tmp_a.as<uint32_t>(), n, ctx->tmp_b.as<uint64_t>()));
         std::vector<uint64_t> rec_off(n + 1);
@@ -2681,8 +2836,12 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
         auto launch = [&](size_t j) -> int {
             const Piece pc = pieces[j];
             const int b = (int)(j & 1);
-            hipLaunchKernelGGL(db_pack_kernel, dim3((uint32_t)((pc.hi - pc.lo + 3) / 4)), dim3(256), 0, ctx->stream, db->d_order, db->d_keys, db->d_key_off,
-                               db->d_entries, db->d_fv32, ctx->tmp_b.as<uint64_t>(), pc.lo, pc.hi, (unsigned char*)d_stage[b]);
+            if (positioned)
+                hipLaunchKernelGGL(db_pack_positions_kernel, dim3((uint32_t)((pc.hi - pc.lo + 3) / 4)), dim3(256), 0, ctx->stream, db->d_order, db->d_keys,
+                                   db->d_key_off, db->d_entries, db->d_positions, db->d_fv32, ctx->tmp_b.as<uint64_t>(), pc.lo, pc.hi, (unsigned char*)d_stage[b]);
+            else
+                hipLaunchKernelGGL(db_pack_kernel, dim3((uint32_t)((pc.hi - pc.lo + 3) / 4)), dim3(256), 0, ctx->stream, db->d_order, db->d_keys, db->d_key_off,
+                                   db->d_entries, db->d_fv32, ctx->tmp_b.as<uint64_t>(), pc.lo, pc.hi, (unsigned char*)d_stage[b]);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipMemcpyAsync(h_stage[b], d_stage[b], rec_off[pc.hi] - rec_off[pc.lo], hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipEventRecord(ev[b], ctx->stream));

@@ -1226,6 +1226,10 @@ struct XpParams {
     const uint32_t* start;         // [(group * S + segment) * NB + bucket] where the unit's range of the bucket starts, relative to
                                    // off[group * NB * stride] (write pass: a workgroup's NB cursors as one contiguous load)
     uint32_t lead_c = 0;           // key-range calls (KK < K): the class of the k-mers' first K - KK symbols (WinCtx::lead_c)
+    // positioned calls (POS write pass): seq[i] = (rank of the matrix in its group) * nwin + window start of pool[i] -- the order in
+    // which explore_group processes the windows (branch_group.cpp:73-86: the first window of the largest score keeps the slot)
+    uint32_t* seq = nullptr;
+    const uint32_t* mat_rank = nullptr;   // [n_mats] rank of each matrix inside its group (the big-list kernel's; the main kernel walks them in order)
 };
 
 // start[(g * S + seg) * NB + b] = off[(g * NB + b) * stride + seg] - off[g * NB * stride]: the scan's offsets of one workgroup's
@@ -1250,7 +1254,7 @@ __global__ __launch_bounds__(256) void xp_unit_starts_kernel(const uint64_t* __r
 // The restriction enters in L (build_halves' LN); R is the full right half.  Where R's codes span more than one bucket
 // (K = 15, 16: 4^8 codes against 32768-slot buckets) a row's pairs go to NSUB = 2 buckets: R (ascending codes as built) is cut
 // into its two bucket ranges, each joined as a list of its own.
-template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool WRITE, int KK = K>
+template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool WRITE, int KK = K, bool POS = false>
 __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1274,6 +1278,7 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
 
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     const uint32_t lane8 = lane * 8u;
+    static_assert(!POS || WRITE, "the sequence numbers are written with the pairs");
     const uint32_t g = blockIdx.x / p.S, seg = blockIdx.x - g * p.S;
     const uint32_t m0 = p.gm_off[g], nm = p.gm_off[g + 1] - m0;
     const uint32_t total_tiles = nm * p.tiles_per_mat;
@@ -1326,6 +1331,7 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
             if (p.flags & 4u) continue;                                        // diagnostics: list building only (nothing is counted or written)
             nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)nL);            // wave-uniform by construction: keep them scalar
             nR_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)nR_all);
+            const uint32_t seq = POS ? q * p.nwin + t0 + w : 0u;               // (gm_list holds a group's matrices in input order: q is the rank)
             // the join of L with R, or with R's bucket range `sub` (NSUB > 1)
             auto join = [&](const uint2* R, uint32_t nR, uint32_t sub) {
             // R sorted by score, descending (rank by counting, in place; ties by position).  fl(a + b) is monotone
@@ -1421,6 +1427,11 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
                         const uint32_t rlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)run, (int)r);
                         const uint32_t rhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(run >> 32), (int)r);
                         const uint2* dst = reinterpret_cast<const uint2*>(((unsigned long long)rhi << 32) | rlo);
+                        // POS: the pair at pool[i] has its sequence number at seq[i] -- the same lanes, half the byte offsets
+                        const void* sdst = nullptr;
+                        if constexpr (POS)
+                            sdst = reinterpret_cast<const void*>(reinterpret_cast<unsigned long long>(xp.seq) +
+                                                                 (((((unsigned long long)rhi << 32) | rlo) - reinterpret_cast<unsigned long long>(p.pool)) >> 1));
                         const uint32_t ax = (uint32_t)__builtin_amdgcn_readlane((int)axm, (int)r);
                         const float ayr = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)a.y, (int)r));
                         auto chunk = [&](auto CHK) {
@@ -1429,12 +1440,14 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
                                 const uint32_t left = cr - (uint32_t)ch * 64u;                       // (> 0 here)
                                 const uint64_t mask = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
                                 store8_lanes<ch * 512>(dst, lane8, ax + rx[ch], __float_as_uint(ayr + ry[ch]), mask);   // :90, the row's passing prefix
+                                if constexpr (POS) store4_lanes<ch * 256>(sdst, lane * 4u, seq, mask);
                             }
                         };
                         if (cr < 64) {                                  // the common case: one store, its lanes = the low cr bits
                             unsigned long long mask;                    // (cr == 0: no lanes, the store is a no-op)
                             asm("s_bfm_b64 %0, %1, 0" : "=s"(mask) : "s"(cr));
                             store8_lanes<0>(dst, lane8, ax + rx[0], __float_as_uint(ayr + ry[0]), mask);
+                            if constexpr (POS) store4_lanes<0>(sdst, lane * 4u, seq, mask);
                             return;
                         }
                         chunk(std::integral_constant<int, 0>{});
@@ -1487,7 +1500,7 @@ __global__ __launch_bounds__(NW * 64) void score_xp_kernel(XpParams xp)
 // the count pass adds a row's passing pairs to that slot (one global atomic per row), the write pass reserves the
 // row's run behind the slot's offset and writes it.  So these pairs, too, are max-reduced in LDS, and nothing
 // touches the tables after the reduce pass.
-template <int SIGMA, int K, uint32_t TBL, bool WRITE, int KK = K>
+template <int SIGMA, int K, uint32_t TBL, bool WRITE, int KK = K, bool POS = false>
 __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams xp)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1512,6 +1525,8 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
         const unsigned long long e = p.ovf_queue[q];
         const uint32_t mat = (uint32_t)(e >> 32), start = (uint32_t)e;
         const uint32_t g = p.mat_slot[mat];
+        uint32_t seq = 0;
+        if constexpr (POS) seq = xp.mat_rank[mat] * p.nwin + start;
         __syncthreads();                                                       // previous window's lists consumed
         const float* src = p.logp + ((size_t)mat * p.sites + start) * SIGMA;
         for (uint32_t i = threadIdx.x; i < K * SIGMA; i += OVF_NW * 64) cols[i] = src[i];
@@ -1581,6 +1596,11 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
                     // (a pointer rebuilt from lane values: told to be global memory, or the stores come out as flat_store -- tests/test_isa.py)
                     typedef unsigned long long __attribute__((address_space(1)))* global_pair_ptr;
                     const global_pair_ptr dst = (global_pair_ptr)(((unsigned long long)dhi << 32) | dlo);
+                    typedef uint32_t __attribute__((address_space(1)))* global_u32_seq_ptr;
+                    global_u32_seq_ptr sdst = nullptr;                         // POS: seq[i] beside pool[i]
+                    if constexpr (POS)
+                        sdst = (global_u32_seq_ptr)(reinterpret_cast<unsigned long long>(xp.seq) +
+                                                    (((((unsigned long long)dhi << 32) | dlo) - reinterpret_cast<unsigned long long>(p.pool)) >> 1));
                     const uint2 au = L[i0 + u];
                     uint32_t done = 0;
                     for (uint32_t jb = 0; jb < nR; jb += 64) {
@@ -1591,6 +1611,7 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
                         const bool pass = j < nR && s > p.eps;
                         const uint64_t m = __ballot(pass);
                         if (pass) dst[done + mbcnt(m)] = (unsigned long long)(au.x * mulR + b.x) | ((unsigned long long)__float_as_uint(s) << 32);
+                        if constexpr (POS) { if (pass) sdst[done + mbcnt(m)] = seq; }
                         done += (uint32_t)__popcll(m);
                     }
                 }
@@ -1668,6 +1689,96 @@ __global__ __launch_bounds__(NT) void reduce_ranges_kernel(uint2* __restrict__ p
         compress_slice<TBL, NT>(tab, nslots, reinterpret_cast<uint32_t*>(pool + r0), mask + (size_t)g * mask_words + (key0 >> 5),
                                 rank + (size_t)g * (mask_words / 2) + (key0 >> 6), vaddr + (size_t)g * (mask_words / 2) + (key0 >> 6), ucnt + gb);
     }
+}
+
+// The positions pass of a positioned call, run over the pairs BEFORE reduce_ranges_kernel consumes them: one workgroup per
+// (group, bucket) keeps, per slot, (score code << 32) | ~seq under a 64-bit LDS max -- the largest score and, among equal score
+// bits, the window processed first (PutScorePos' key, in LDS) -- and leaves the winners' window starts (seq % nwin) in slot order at
+// pvals[r0 ..), r0 = the range's first pair: the index reduce_ranges_kernel's compressed form gives the same slot's score code
+// (rank + popcount of the occupancy bits below), so pvaddr[g][block] = &pvals[r0 + rank] stands beside vaddr[g][block] and the
+// key-major writer transposes the positions exactly as it does the scores.  The values carry bit 31: the writer's score decoding
+// (dec_score_bits) takes it off again, so that kernel runs over them unchanged.
+// An 8-byte table of TBL slots does not fit LDS above 16384 slots: such a slice is reduced in two trips over its pairs, each
+// keeping the pairs of its half of the slots (POS_SUB slots, whole 64-slot blocks).
+template <uint32_t TBL> constexpr uint32_t pos_sub_slots() { return TBL <= 16384u ? TBL : TBL / 2; }
+template <uint32_t TBL> constexpr uint32_t pos_sub_blocks() { return (pos_sub_slots<TBL>() + 63) / 64; }
+template <uint32_t TBL, int NT>
+__global__ __launch_bounds__(NT) void reduce_ranges_pos_kernel(const uint2* __restrict__ pool, const uint32_t* __restrict__ seq,
+                                                              const uint64_t* __restrict__ off, uint32_t S, uint32_t NB, uint64_t T,
+                                                              uint32_t nwin, uint64_t mask_words, uint32_t* __restrict__ pvals,
+                                                              uint64_t* __restrict__ pvaddr)
+{
+    constexpr uint32_t SUB = pos_sub_slots<TBL>(), NBLK = pos_sub_blocks<TBL>();
+    static_assert(SUB == TBL || (SUB % 64 == 0 && SUB * 2 == TBL), "a trip covers whole 64-slot blocks");
+    static_assert(NBLK <= 256, "the block counts are scanned by one wavefront, four per lane");
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned long long* tab = reinterpret_cast<unsigned long long*>(smem);     // [NBLK * 64]
+    uint32_t* bc = reinterpret_cast<uint32_t*>(tab + (size_t)NBLK * 64);       // [NBLK + 1]: slots before each block; [NBLK]: the trip's slots
+    const uint32_t gb = blockIdx.x;
+    const uint32_t g = gb / NB, b = gb - g * NB;
+    const uint64_t key0 = (uint64_t)b * TBL;
+    const uint32_t nslots = (uint32_t)min((uint64_t)TBL, T - key0);
+    const uint64_t r0 = off[(size_t)gb * S], r1 = off[(size_t)gb * S + S];
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t k0 = (uint32_t)key0;
+    uint32_t base = 0;                                                          // non-empty slots of the trips before
+    for (uint32_t s0 = 0; s0 < nslots; s0 += SUB) {
+        for (uint32_t z = threadIdx.x; z < NBLK * 64; z += NT) tab[z] = 0ull;
+        __syncthreads();
+        for (uint64_t i = r0 + threadIdx.x; i < r1; i += NT) {
+            const uint2 pr = pool[i];
+            const uint32_t slot = pr.x - k0 - s0;
+            if (slot < SUB)
+                atomicMax(&tab[slot], ((unsigned long long)enc_score_bits(pr.y) << 32) | (unsigned long long)(0xFFFFFFFFu - seq[i]));
+        }
+        __syncthreads();
+        const uint32_t nblk = (min(SUB, nslots - s0) + 63) / 64;
+        for (uint32_t blk = wave; blk < nblk; blk += NT / 64) {
+            const uint64_t m = ballot64(tab[blk * 64 + lane] != 0ull);
+            if (lane == 0) bc[blk] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        if (wave == 0) {                                                        // exclusive scan of the block counts (four adjacent blocks per lane)
+            uint32_t loc[4], sum = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t idx = lane * 4 + j;
+                loc[j] = sum;
+                sum += idx < nblk ? bc[idx] : 0u;
+            }
+            uint32_t incl = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(incl, o, 64);
+                if (lane >= (uint32_t)o) incl += up;
+            }
+            const uint32_t excl = incl - sum;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t idx = lane * 4 + j;
+                if (idx < nblk) bc[idx] = base + excl + loc[j];
+            }
+            if (lane == 63) bc[NBLK] = incl;
+        }
+        __syncthreads();
+        uint64_t* const va = pvaddr + (size_t)g * (mask_words / 2) + ((key0 + s0) >> 6);
+        for (uint32_t blk = wave; blk < nblk; blk += NT / 64) {
+            const unsigned long long v = tab[blk * 64 + lane];
+            const uint64_t m = ballot64(v != 0ull);
+            uint32_t* const dst = pvals + r0 + bc[blk];
+            if (v != 0ull) dst[mbcnt(m)] = ((0xFFFFFFFFu - (uint32_t)v) % nwin) | 0x80000000u;
+            if (lane == 0) va[blk] = reinterpret_cast<uint64_t>(dst);
+        }
+        base += bc[NBLK];
+        __syncthreads();                                                        // bc and tab are rewritten by the next trip
+    }
+}
+
+// the window starts out of the (branch, position) records a key-major writer pass over the position values left
+__global__ __launch_bounds__(256) void extract_positions_kernel(const uint2* __restrict__ in, uint64_t n, uint32_t* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[i].y;
 }
 
 }  // namespace ipkgpu

@@ -152,7 +152,8 @@ def init_native_comm(engine, dist, world, rank):
     return True
 
 
-def build_db_shard(engine, logp, mat_group, k, log_eps, sigma, dist=None, world=1, rank=0, overlap=True, pieces=None, agreed=False):
+def build_db_shard(engine, logp, mat_group, k, log_eps, sigma, dist=None, world=1, rank=0, overlap=True, pieces=None, agreed=False,
+                   positions=False):
     """Scores this rank's groups and returns (this rank's database shard, parts) -- the state
     `_phylo_kmer_db` has after explore_kmers (db_builder.cpp:576-627), sharded by k-mer owner.
 
@@ -160,9 +161,14 @@ def build_db_shard(engine, logp, mat_group, k, log_eps, sigma, dist=None, world=
     exchange of one range's blocks runs while the next range is being scored -- only the last range's transfer is
     exposed; the merge takes pieces x world sources in the order (rank 0 piece 0, rank 0 piece 1, ..., rank 1 piece 0, ...),
     which is global group order.  All ranks use the same piece count (agree_on_pieces: two small all-reduces per call, unless the
-    caller settled the count beforehand -- `pieces` from agree_on_pieces() with agreed=True, as a loop over equally shaped calls does)."""
+    caller settled the count beforehand -- `pieces` from agree_on_pieces() with agreed=True, as a loop over equally shaped calls does).
+    positions=True (one rank): the positioned database of --keep-positions."""
+    if positions and world != 1:
+        raise ValueError("positions: one rank only (the exchange does not carry positions yet)")
     if world == 1:
-        parts = engine.score_groups_keymajor(logp, mat_group, k, log_eps, n_owners=1)
+        # positions=True: every entry's window start rides along (Db.positions()), one scoring pass all the same
+        score = engine.score_groups_keymajor_positions if positions else engine.score_groups_keymajor
+        parts = score(logp, mat_group, k, log_eps, n_owners=1)
         return engine.db_from_parts(parts, sigma, k), parts
 
     import time

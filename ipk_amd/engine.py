@@ -314,6 +314,14 @@ def _bind_keymajor(L):
     L.ipkgpu_score_groups_keyrange_device.restype = C.c_int
     L.ipkgpu_score_groups_keyrange_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
                                                       C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_score_groups_keymajor_positions_device.restype = C.c_int
+    L.ipkgpu_score_groups_keymajor_positions_device.argtypes = L.ipkgpu_score_groups_keymajor_device.argtypes
+    L.ipkgpu_parts_positions_device.restype = C.c_void_p
+    L.ipkgpu_parts_positions_device.argtypes = [C.c_void_p]
+    L.ipkgpu_db_positions.restype = u32p
+    L.ipkgpu_db_positions.argtypes = [C.c_void_p]
+    L.ipkgpu_db_positions_device.restype = C.c_void_p
+    L.ipkgpu_db_positions_device.argtypes = [C.c_void_p]
     L.ipkgpu_parts_key_base.restype = C.c_uint64
     L.ipkgpu_parts_key_base.argtypes = [C.c_void_p]
     L.ipkgpu_parts_num_owners.restype = C.c_uint32
@@ -409,6 +417,8 @@ ABI_SYMBOLS += [
     "ipkgpu_exchange_begin", "ipkgpu_exchange_merge", "ipkgpu_xfer_exposed_ms", "ipkgpu_xfer_free",
     "ipkgpu_comm_available", "ipkgpu_comm_prepare",
     "ipkgpu_max_k_keyrange", "ipkgpu_score_groups_keyrange_device", "ipkgpu_parts_key_base",
+    "ipkgpu_score_groups_keymajor_positions_device", "ipkgpu_parts_positions_device", "ipkgpu_db_positions",
+    "ipkgpu_db_positions_device",
 ]
 
 
@@ -444,6 +454,17 @@ class Parts:
     def entries_tensor(self):
         """torch view [num_entries, 2] int32 (branch, score bits)."""
         return _device_tensor(self.entries_ptr(), (max(self.num_entries, 0), 2), "int32", self)
+
+    def positions_ptr(self):
+        """Device pointer of the entries' window starts; None for parts of a call without positions."""
+        return self._lib.ipkgpu_parts_positions_device(self._h)
+
+    def positions_tensor(self):
+        """torch view [num_entries] int32 of the window starts, aligned with entries_tensor (score_groups_keymajor_positions)."""
+        p = self.positions_ptr()
+        if not p:
+            raise IpkGpuError(1, "these parts carry no positions")
+        return _device_tensor(p, (max(self.num_entries, 0),), "int32", self)
 
     def free(self):
         if self._h:
@@ -482,6 +503,17 @@ class Db:
             return np.zeros(0, np.uint32), np.zeros(0, np.float32)
         e = np.ctypeslib.as_array(self._lib.ipkgpu_db_entries(self._h), shape=(self.num_entries, 2))
         return e[:, 0].copy(), e[:, 1].copy().view(np.float32)
+
+    def positions(self):
+        """Window starts u32 [n] aligned with entries(); None for a database without positions."""
+        if not self._lib.ipkgpu_db_positions_device(self._h):
+            return None
+        if self.num_entries == 0:
+            return np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(self._lib.ipkgpu_db_positions(self._h), shape=(self.num_entries,))
+
+    def positions_device_ptr(self):
+        return self._lib.ipkgpu_db_positions_device(self._h)
 
     def filter_mif0(self, engine, total_num_groups, threshold):
         """MIF0 filter values + k-mer order (filter.cpp:55-119, db_builder.cpp:281-284) on the device."""
@@ -550,7 +582,8 @@ def _device_tensor(ptr, shape, dtype, owner):
     return t
 
 
-def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None, keyrange=None):
+def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None, keyrange=None,
+                           positions=False):
     """Scoring pass with key-major, owner-split output (see include/ipkgpu.h). logp: torch CUDA tensor
     [n_mats, sites, sigma] float32 or a raw device pointer with explicit shape.  keyrange = (lead, cls): the key-range pass of
     the k-mers whose first `lead` symbols spell `cls` (one owner; ipkgpu_score_groups_keyrange_device)."""
@@ -578,6 +611,10 @@ def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=
         rc = self._lib.ipkgpu_score_groups_keyrange_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
                                                            mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
                                                            C.c_float(log_eps), lead, cls, C.byref(out))
+    elif positions:
+        rc = self._lib.ipkgpu_score_groups_keymajor_positions_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
+                                                                     mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                                     C.c_float(log_eps), n_owners, C.byref(out))
     else:
         rc = self._lib.ipkgpu_score_groups_keymajor_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
                                                            mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
@@ -703,4 +740,14 @@ def _score_groups_keyrange(self, logp, mat_group, k, log_eps, lead, cls):
 
 
 Engine.score_groups_keyrange = _score_groups_keyrange
+
+
+def _score_groups_keymajor_positions(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None):
+    """score_groups_keymajor with every entry's window start riding along (Parts.positions_tensor, Db.positions): one scoring
+    pass on the device (include/ipkgpu.h, ipkgpu_score_groups_keymajor_positions_device).  One owner only."""
+    return _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=n_owners, sigma=sigma, sites=sites, n_mats=n_mats,
+                                  positions=True)
+
+
+Engine.score_groups_keymajor_positions = _score_groups_keymajor_positions
 Engine.merge_parts = _merge_parts

@@ -1,7 +1,7 @@
 """Randomised parity runs against the CPU oracle (a diagnostic tool: the oracle only checks, nothing here is product code).
 Every case: random alphabet, k, sites, matrices, grouping, column concentration, threshold, owners, batch size, prefix-kernel shape;
-the per-branch result (ipkgpu_score_groups) and the key-major database shards (ipkgpu_score_groups_keymajor + db_from_parts / merge)
-must equal the oracle's bit for bit.  Usage: python tools/fuzz_parity.py [seconds=240] [seed=1]"""
+the per-branch result (ipkgpu_score_groups), the key-major database shards (ipkgpu_score_groups_keymajor + db_from_parts / merge) and,
+for a third of the cases, the positioned database (ipkgpu_score_groups_keymajor_positions) must equal the oracle's bit for bit.  Usage: python tools/fuzz_parity.py [seconds=240] [seed=1]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -104,6 +104,24 @@ def _one(rng, eng, max_k_dna, fails, log):
                 assert np.array_equal(res.keys()[a:b], keys) and np.array_equal(res.scores()[a:b].view(np.uint32), scores.view(np.uint32)), f"positions: group {gid} differs"
                 assert np.array_equal(res.positions()[a:b], pos), f"positions of group {gid} differ"
             res.free()
+        if (n_mats + sites + k) % 3 == 0 and (sigma == 20 or k >= 4):
+            # the positioned key-major database (one scoring pass; drawn from the case's shape, so the other draws stay as they were):
+            # the plain database's keys and entries, plus explore_group_pos' positions
+            parts = eng.score_groups_keymajor_positions(mats, mat_group, k, eps)
+            assert parts.emitted == emitted, "positioned database: emitted"
+            db = eng.db_from_parts(parts, sigma, k)
+            keys, off, br, sc = dbo.db_shard_arrays(full, sigma, k, 0, 1)
+            b_, s_ = db.entries()
+            assert np.array_equal(db.keys(), keys) and np.array_equal(db.key_offsets(), off), "positioned database: keys"
+            assert np.array_equal(b_, br) and np.array_equal(s_.view(np.uint32), sc), "positioned database: entries"
+            want = np.empty(len(br), dtype=np.uint32)
+            entry_key = np.repeat(keys, np.diff(off.astype(np.int64)))
+            for gid in order:
+                gk, _, gp, _ = co.explore_group_pos(mats[mat_group == gid], k, eps)
+                sel = np.flatnonzero(br == gid)
+                want[sel] = gp[np.searchsorted(gk, entry_key[sel])]
+            assert np.array_equal(db.positions(), want), "positioned database: positions"
+            db.free(); parts.free()
     except ipk_amd.IpkGpuError as ex:
         if "half list exceeds" in str(ex) and k >= 13:
             pass                                        # the documented cap of k = 13, 14
