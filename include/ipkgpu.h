@@ -237,13 +237,25 @@ int ipkgpu_score_groups_keyrange_device(ipkgpu_ctx* ctx, const float* logp_dev, 
  * order, entry order and score bits equal those of ipkgpu_score_groups_keymajor_device on the same input; the position rides
  * along through ONE scoring pass (the exact partition with compressed tables: sequence numbers beside the pairs, an LDS reduce on
  * (score, first window), the key-major writer run over the position values as well).
- * n_owners must be 1 (the exchange does not carry positions); supported where the exact partition exists: amino acids k = 2..6,
+ * n_owners must be 1 and n_mats > 0 here (several owners: ipkgpu_score_groups_keymajor_positions_owners_device below); supported where the exact partition exists: amino acids k = 2..6,
  * DNA k = 4..14; a group's matrices x windows must stay below 2^32.  Anything else: IPKGPU_ERR_INVALID with a message.
  * ipkgpu_db_from_parts moves the positions into the database with the entries; ipkgpu_db_write then writes the positioned file.
  */
 int ipkgpu_score_groups_keymajor_positions_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
                                                   uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
                                                   uint32_t n_owners, ipkgpu_parts** out);
+/*
+ * The positioned call split by owner, for several ranks: the same arguments, the same path and the same refusals as
+ * ipkgpu_score_groups_keymajor_positions_device, with any n_owners >= 1.  counts [n_owners][slots] and entries are those of
+ * ipkgpu_score_groups_keymajor_device(..., n_owners); ipkgpu_parts_positions_device gives the window starts aligned entry for entry
+ * with the entries, block o being [owner_offsets[o], owner_offsets[o + 1]) of both.  A group's matrices are all in one call, so the
+ * tie rule needs nothing from other ranks: the positions only travel (ipkgpu_exchange_begin) and are merged
+ * (ipkgpu_merge_parts_positions_ptrs) beside their entries.  n_mats == 0 gives empty positioned parts (zero counts, no entries,
+ * ipkgpu_parts_positions_device non-NULL): a rank or a piece without groups takes part in a positioned exchange with them.
+ */
+int ipkgpu_score_groups_keymajor_positions_owners_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                                         uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                                         uint32_t n_owners, ipkgpu_parts** out);
 /* u32 [entries] window starts aligned entry for entry with ipkgpu_parts_entries_device; NULL for parts of the other calls */
 const uint32_t* ipkgpu_parts_positions_device(const ipkgpu_parts* p);
 /* lead_class * sigma^(k - lead_symbols) for key-range parts; 0 for other parts */
@@ -273,6 +285,12 @@ int ipkgpu_merge_parts(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
  * counts row [slots] (device), entries_dev[s] = its entry block (device).  Both pointer arrays live in HOST memory. */
 int ipkgpu_merge_parts_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, uint32_t n_sources,
                             const uint32_t* const* counts_dev, const void* const* entries_dev, ipkgpu_db** out);
+/* ipkgpu_merge_parts_ptrs over positioned sources: positions_dev[s] = source s's window starts (u32, device), aligned entry for
+ * entry with entries_dev[s].  Every position is copied beside its entry in the same pass (merge_copy_pos_kernel), and the database
+ * has them (ipkgpu_db_positions), so ipkgpu_db_filter_mif0 and ipkgpu_db_write treat it as ipkgpu_db_from_parts' positioned one. */
+int ipkgpu_merge_parts_positions_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, uint32_t n_sources,
+                                      const uint32_t* const* counts_dev, const void* const* entries_dev,
+                                      const uint32_t* const* positions_dev, ipkgpu_db** out);
 
 /* ---- the exchange step itself: RCCL over xGMI, inside the library ------------------------------------------------
  * One process per GPU.  Rank 0 draws an id (ipkgpu_comm_unique_id) and hands its 128 bytes to the other ranks by any means
@@ -280,6 +298,10 @@ int ipkgpu_merge_parts_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_
  * calls ipkgpu_score_groups_keymajor_device(..., n_owners = world) and ipkgpu_exchange_begin, which enqueues block o -> rank o
  * (grouped ncclSend/ncclRecv on the communicator's own stream) and returns, so the transfer runs under the next piece's
  * scoring; ipkgpu_exchange_merge waits for the pieces and merges (rank, piece)-ordered sources into this rank's shard.
+ * Positioned pieces (ipkgpu_score_groups_keymajor_positions_owners_device) send their window starts beside the entries, one more
+ * send/receive pair per peer in the same group; the size word that travels first carries "positioned" in bit 63, and a rank whose
+ * peers' flags differ from its own fails ipkgpu_exchange_begin with IPKGPU_ERR_INVALID before the payload group.
+ * ipkgpu_exchange_merge gives a database with positions when all pieces are positioned and refuses a mixture (IPKGPU_ERR_INVALID).
  * All ranks must use the same number of pieces.  RCCL is loaded at run time: IPKGPU_ERR_NODEVICE if it is not there.
  * Failure must be symmetric, or the healthy ranks wait for ever inside a collective: everything that can fail on one rank
  * alone (loading RCCL, the exchange stream and buffers) is done by ipkgpu_comm_prepare, BEFORE the collective
@@ -440,7 +462,10 @@ const char* ipkgpu_db_write_last_error(void);
  * filter values computed, in its filter order) as a database file of its own with ipkgpu_db_write / ipkgpu_db_write_host
  * (any header: only the totals are read back); one rank then merges the P shard files by (filter value, key) into `path`
  * under header `h`, streaming through bounded buffers: resident memory does not depend on the number of entries, and the
- * result equals, byte for byte, the file one GPU writes for the same input.  Host code, no GPU needed. */
+ * result equals, byte for byte, the file one GPU writes for the same input.  Host code, no GPU needed.
+ * Positioned shards (the positions flag in their headers; records of 16 + 10 n bytes) merge into a positioned file, the flag
+ * set in its header.  A mixture of positioned and plain shards is IPKGPU_ERR_INVALID, and so are positioned shards under
+ * IPKGPU_IPK_PROTOCOL_VERSION=0, whose layout has no flag to read. */
 int ipkgpu_db_merge_files(const ipkgpu_db_header* h, const char* const* shard_paths, uint32_t n_shards, const char* path,
                           uint64_t* total_kmers, uint64_t* total_entries, uint64_t* bytes_written);
 const char* ipkgpu_db_merge_last_error(void);

@@ -58,9 +58,10 @@ def ipk():
 @click.option("--ar-only", is_flag=True, help="(ignored)")
 @click.option("--ar-config", type=click.Path(), help="(ignored)")
 @click.option("--keep-positions", is_flag=True,
-              help="(ipk-aa-pos; amino acids, one GPU) every database entry carries the window position of its kept score "
+              help="(ipk-aa-pos; amino acids) every database entry carries the window position of its kept score "
                    "(db_builder.cpp:655-662,687-689): the position rides along through the one scoring pass on the device "
-                   "(ipkgpu_score_groups_keymajor_positions_device); the entry layout (branch, score, u16 position) is a guess like the rest of the file")
+                   "(ipkgpu_score_groups_keymajor_positions_device; several ranks: the positions travel through the k-mer-keyed exchange beside "
+                   "their entries); the entry layout (branch, score, u16 position) is a guess like the rest of the file")
 @click.option("--uncompressed", is_flag=True, help="(ignored, as in the reference)")
 @click.option("--threads", type=int, default=0,
               help="host threads of the probability loader [0 = every core this process may run on, divided among the ranks of a node; the reference's --threads only "
@@ -84,9 +85,6 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
 
     if keep_positions and states == "nucl":
         raise click.UsageError("--keep-positions is not supported for DNA.")              # ipk.py:281-282
-    if keep_positions and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("--keep-positions: the positioned database is built by ONE process (the k-mer-keyed exchange between ranks "
-                               "does not carry positions yet); run without torchrun")
     if merge_branches:
         raise click.UsageError("--merge-branches is not supported (the reference only guards it, main.cpp:31-37)")
     from ipk_amd import tree as T
@@ -216,7 +214,9 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
         order_p = np.argsort(dbfile.filter_sort_code(fv_p, keys_db), kind="stable")
 
         def write_shard(file):
-            dbfile.write_db_positions(file, seq_name, tree_index, newick, k, omega, keys_db, db.key_offsets(), br_db, sc_db, pos_db, fv_p, order_p)
+            one = world == 1
+            dbfile.write_db_positions(file, seq_name, tree_index if one else [], newick if one else "", k, omega, keys_db, db.key_offsets(),
+                                      br_db, sc_db, pos_db, fv_p, order_p)
     elif filter_ == "mif0":
         # (--keep-positions: `db` carries positions, and the device writer packs the positioned records)
         # records packed on the device in filter order and streamed to the file (ipkgpu_db_write): the database itself on one

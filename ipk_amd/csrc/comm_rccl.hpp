@@ -4,6 +4,9 @@
 // (ipk/src/branch_group.cpp:104-107), merge_batch (:45-70), merge_stage2 (ipk/src/db_builder.cpp:392-458).  Here rank r scores
 // a contiguous range of branch groups, ipkgpu_score_groups_keymajor_device(..., n_owners = world) leaves its entries split by
 // owner, and block o travels to rank o: grouped ncclSend / ncclRecv, one pair per peer (direct xGMI links, no ring).
+// Positioned parts (ipkgpu_score_groups_keymajor_positions_owners_device) send block o of their window starts beside it: one more
+// pair per peer in the same group.  Bit 63 of the size word says "positioned", so that the ranks find a disagreement BEFORE any of
+// them enters a grouped transfer the others do not.
 //
 // RCCL is bound at run time (dlopen of librccl.so.1 -- the copy the process already holds, e.g. PyTorch's, is reused), so a
 // single-GPU build never touches it and a missing library is an error code, not a load failure.
@@ -64,6 +67,7 @@ struct ipkgpu_xfer {
     uint64_t slots = 0;
     uint32_t* d_rcounts = nullptr;        // [world][slots]: row s = source rank s's counts of my keys
     uint2* d_rentries = nullptr;          // sources' blocks back to back
+    uint32_t* d_rpositions = nullptr;     // positioned pieces: the sources' window starts, laid out as d_rentries; else null
     std::vector<uint64_t> roff;           // [world + 1] entry offsets of the sources' blocks
     hipEvent_t done = nullptr;
     double t_exposed_ms = 0;
@@ -165,14 +169,17 @@ void ipkgpu_xfer_free(ipkgpu_xfer* x)
     if (x->ctx) {
         (void)hipSetDevice(x->ctx->device);
         if (x->done) { (void)hipEventSynchronize(x->done); (void)hipEventDestroy(x->done); }
-        ctx_release(x->ctx, x->d_rcounts); ctx_release(x->ctx, x->d_rentries);
+        ctx_release(x->ctx, x->d_rcounts); ctx_release(x->ctx, x->d_rentries); ctx_release(x->ctx, x->d_rpositions);
     }
     delete x;
 }
 
 // Starts the exchange of one piece: block o of `parts` (counts row o, entries [owner_off[o], owner_off[o+1])) goes to rank o.
 // Returns after the transfers have been ENQUEUED on the communicator's stream; `parts` must stay alive until
-// ipkgpu_exchange_merge.  The entry counts travel first (one u64 per peer) because the receive sizes must be known on the host.
+// ipkgpu_exchange_merge.  The entry counts travel first (one u64 per peer) because the receive sizes must be known on the host;
+// bit 63 of that word is set by a rank whose parts are positioned.  A rank that finds a peer's flag different from its own fails
+// with IPKGPU_ERR_INVALID before the payload group (ipkgpu_exchange_begin then aborts the communicator, as for any failure here).
+static constexpr uint64_t XFER_POSITIONED = 1ull << 63;
 static int exchange_begin_impl(ipkgpu_ctx* ctx, ipkgpu_comm* c, ipkgpu_parts* parts, ipkgpu_xfer** out);
 
 int ipkgpu_exchange_begin(ipkgpu_ctx* ctx, ipkgpu_parts* parts, ipkgpu_xfer** out)
@@ -204,6 +211,11 @@ static int exchange_begin_impl(ipkgpu_ctx* ctx, ipkgpu_comm* c, ipkgpu_parts* pa
     // 1. sizes: send_counts[o] to rank o, one u64 each way
     std::vector<uint64_t> sizes(2 * (size_t)P);
     exchange_split(parts->owner_off.data(), P, sizes.data());
+    const bool positioned = parts->d_positions != nullptr;
+    for (uint32_t o = 0; o < P; ++o) {
+        if (sizes[o] & XFER_POSITIONED) return fail(ctx, IPKGPU_ERR_INVALID, "a block of 2^63 entries cannot be exchanged");
+        if (positioned) sizes[o] |= XFER_POSITIONED;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(ctx, hipMemcpyAsync(c->d_sizes, sizes.data(), (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
     NCCL_TRY(ctx, g_rccl.GroupStart());
@@ -215,11 +227,18 @@ static int exchange_begin_impl(ipkgpu_ctx* ctx, ipkgpu_comm* c, ipkgpu_parts* pa
     HIP_TRY(ctx, hipMemcpyAsync(sizes.data() + P, c->d_sizes + P, (size_t)P * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(ctx, hipStreamSynchronize(c->stream));          // also waits for the previous piece's transfer: what scoring did not hide
     x->t_exposed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (uint32_t s = 0; s < P; ++s) {
+        if (((sizes[P + s] & XFER_POSITIONED) != 0) != positioned)
+            return fail(ctx, IPKGPU_ERR_INVALID, "rank %u exchanges %s parts, this rank (%d) %s ones: every rank must score a piece with the same call",
+                        s, positioned ? "plain" : "positioned", c->rank, positioned ? "positioned" : "plain");
+        sizes[s] &= ~XFER_POSITIONED; sizes[P + s] &= ~XFER_POSITIONED;
+    }
     x->roff.assign((size_t)P + 1, 0);
     for (uint32_t s = 0; s < P; ++s) x->roff[s + 1] = x->roff[s] + sizes[P + s];
     // 2. payload: counts rows (fixed size) and entry blocks
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&x->d_rcounts, std::max<uint64_t>((uint64_t)P * x->slots, 1) * 4));
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&x->d_rentries, std::max<uint64_t>(x->roff[P], 1) * 8));
+    if (positioned) HIP_TRY(ctx, ctx_alloc(ctx, (void**)&x->d_rpositions, std::max<uint64_t>(x->roff[P], 1) * 4));
     HIP_TRY(ctx, hipEventCreateWithFlags(&x->done, hipEventDisableTiming));
     NCCL_TRY(ctx, g_rccl.GroupStart());
     for (uint32_t o = 0; o < P; ++o) {
@@ -227,6 +246,8 @@ static int exchange_begin_impl(ipkgpu_ctx* ctx, ipkgpu_comm* c, ipkgpu_parts* pa
         NCCL_TRY(ctx, g_rccl.Recv(x->d_rcounts + (size_t)o * x->slots, x->slots, ncclUint32, (int)o, c->comm, c->stream));
         if (sizes[o]) NCCL_TRY(ctx, g_rccl.Send(parts->d_entries + parts->owner_off[o], sizes[o], ncclUint64, (int)o, c->comm, c->stream));
         if (sizes[P + o]) NCCL_TRY(ctx, g_rccl.Recv(x->d_rentries + x->roff[o], sizes[P + o], ncclUint64, (int)o, c->comm, c->stream));
+        if (positioned && sizes[o]) NCCL_TRY(ctx, g_rccl.Send(parts->d_positions + parts->owner_off[o], sizes[o], ncclUint32, (int)o, c->comm, c->stream));
+        if (positioned && sizes[P + o]) NCCL_TRY(ctx, g_rccl.Recv(x->d_rpositions + x->roff[o], sizes[P + o], ncclUint32, (int)o, c->comm, c->stream));
     }
     NCCL_TRY(ctx, g_rccl.GroupEnd());
     HIP_TRY(ctx, hipEventRecord(x->done, c->stream));
@@ -239,10 +260,15 @@ double ipkgpu_xfer_exposed_ms(const ipkgpu_xfer* x) { return x ? x->t_exposed_ms
 
 int ipkgpu_merge_parts_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, uint32_t n_sources,
                             const uint32_t* const* counts_dev, const void* const* entries_dev, ipkgpu_db** out);
+int ipkgpu_merge_parts_positions_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, uint32_t n_sources,
+                                      const uint32_t* const* counts_dev, const void* const* entries_dev, const uint32_t* const* positions_dev,
+                                      ipkgpu_db** out);
 
 // Waits for the pieces' transfers and merges them into this rank's database shard: sources in the order (rank 0 piece 0,
 // rank 0 piece 1, ..., rank 1 piece 0, ...) = global group order, the order the reference appends entries
 // (db_builder.cpp:606-618,685-694).  *exposed_ms (optional): time this call waited for transfers.
+// Pieces that are all positioned give a database with positions (ipkgpu_merge_parts_positions_ptrs); a mixture of positioned and
+// plain pieces is refused.
 int ipkgpu_exchange_merge(ipkgpu_ctx* ctx, ipkgpu_xfer* const* xfers, uint32_t n_pieces, uint32_t sigma, uint32_t k, ipkgpu_db** out,
                           double* exposed_ms)
 {
@@ -262,12 +288,20 @@ int ipkgpu_exchange_merge(ipkgpu_ctx* ctx, ipkgpu_xfer* const* xfers, uint32_t n
         for (uint32_t j = 0; j < n_pieces; ++j) *exposed_ms += xfers[j]->t_exposed_ms;
     }
     const uint32_t P = (uint32_t)c->world;
-    std::vector<const uint32_t*> cp; std::vector<const void*> ep;
+    const bool positioned = xfers[0]->d_rpositions != nullptr;
+    for (uint32_t j = 1; j < n_pieces; ++j)
+        if ((xfers[j]->d_rpositions != nullptr) != positioned)
+            return fail(ctx, IPKGPU_ERR_INVALID, "pieces with and without positions cannot be merged into one database (piece 0 %s, piece %u %s)",
+                        positioned ? "positioned" : "plain", j, positioned ? "plain" : "positioned");
+    std::vector<const uint32_t*> cp; std::vector<const void*> ep; std::vector<const uint32_t*> pp;
     for (uint32_t s = 0; s < P; ++s)
         for (uint32_t j = 0; j < n_pieces; ++j) {
             cp.push_back(xfers[j]->d_rcounts + (size_t)s * xfers[j]->slots);
             ep.push_back(xfers[j]->d_rentries + xfers[j]->roff[s]);
+            if (positioned) pp.push_back(xfers[j]->d_rpositions + xfers[j]->roff[s]);
         }
+    if (positioned)
+        return ipkgpu_merge_parts_positions_ptrs(ctx, sigma, k, (uint32_t)c->rank, P, (uint32_t)cp.size(), cp.data(), ep.data(), pp.data(), out);
     return ipkgpu_merge_parts_ptrs(ctx, sigma, k, (uint32_t)c->rank, P, (uint32_t)cp.size(), cp.data(), ep.data(), out);
 }
 

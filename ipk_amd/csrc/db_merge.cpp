@@ -7,7 +7,8 @@
 // already in ITS filter order, as a database file of its own (ipkgpu_db_write / ipkgpu_db_write_host).  This merge reads the P
 // shards through bounded buffers, always copies the record with the smallest (filter value, key) next, and writes the header
 // with the summed totals first -- the file one GPU writes for the same input, byte for byte, with a resident set that does not
-// depend on the number of entries.
+// depend on the number of entries.  Positioned shards (the header's positions flag; records of 16 + 10 n bytes) merge the same way
+// into a positioned file; a mixture of positioned and plain shards is refused.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -30,6 +31,7 @@ struct ShardReader {
     uint64_t left = 0;                 // records not yet handed out
     uint64_t key = 0;                  // sort key of the current record
     uint64_t rec_bytes = 0;            // its size
+    bool positioned = false;           // the shard's header has the positions flag: entries of (branch, score, position)
     ~ShardReader() { if (f) fclose(f); }
 
     // at least n unconsumed bytes in the buffer (false: the file ends first)
@@ -53,7 +55,8 @@ struct ShardReader {
         uint32_t w[4];
         memcpy(w, buf.data() + lo, sizeof w);
         const uint64_t n = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-        rec_bytes = ipkfmt::record_bytes(n);
+        if (n > ((uint64_t)1 << 40)) return false;                     // (not a record of this layout: no such entry count)
+        rec_bytes = positioned ? ipkfmt::record_bytes_positions(n) : ipkfmt::record_bytes(n);
         key = ipkfmt::record_sort_key(w[0], w[1]);
         return need((size_t)rec_bytes);
     }
@@ -73,13 +76,25 @@ int ipkgpu_db_merge_files(const ipkgpu_db_header* h, const char* const* shard_pa
     constexpr size_t IN_BUF = (size_t)4 << 20, OUT_BUF = (size_t)16 << 20;
     std::vector<std::unique_ptr<ShardReader>> in;
     uint64_t nk = 0, ne = 0;
+    bool positioned = false;
     for (uint32_t s = 0; s < n_shards; ++s) {
         std::unique_ptr<ShardReader> r(new ShardReader());
         r->f = fopen(shard_paths[s], "rb");
         if (!r->f) { g_merge_err = std::string("cannot open shard ") + shard_paths[s]; return IPKGPU_ERR_INVALID; }
         setvbuf(r->f, nullptr, _IONBF, 0);                             // (own buffering: no second copy through stdio)
         uint64_t k = 0, e = 0;
-        if (!ipkfmt::read_head(r->f, k, e)) { g_merge_err = std::string("not a database shard: ") + shard_paths[s]; return IPKGPU_ERR_INVALID; }
+        if (!ipkfmt::read_head(r->f, k, e, &r->positioned)) {
+            g_merge_err = std::string("not a database shard: ") + shard_paths[s];
+            // (the layout of version 0 has no positions flag: a positioned shard, written with the protocol word, ends here)
+            if (ipkfmt::protocol_version() == 0) g_merge_err += " (IPKGPU_IPK_PROTOCOL_VERSION=0: no protocol word and no positions flag are read, so positioned shards cannot be merged)";
+            return IPKGPU_ERR_INVALID;
+        }
+        if (s == 0) positioned = r->positioned;
+        if (r->positioned != positioned) {
+            g_merge_err = std::string("positioned and plain shards cannot be merged into one database: ") + shard_paths[s] + (r->positioned ? " has positions, " : " has none, ") +
+                          shard_paths[0] + (positioned ? " has" : " has none");
+            return IPKGPU_ERR_INVALID;
+        }
         r->left = k; nk += k; ne += e;
         r->buf.resize(IN_BUF);
         if (!r->next()) { g_merge_err = std::string("truncated shard: ") + shard_paths[s]; return IPKGPU_ERR_INVALID; }
@@ -90,7 +105,7 @@ int ipkgpu_db_merge_files(const ipkgpu_db_header* h, const char* const* shard_pa
     struct Close { FILE*& f; ~Close() { if (f) fclose(f); } } closer{out};
     setvbuf(out, nullptr, _IONBF, 0);
     const std::vector<uint8_t> head = ipkfmt::file_head(h->sequence_type, h->tree_index_size, h->tree_num_nodes, h->tree_subtree_length,
-                                                        h->newick, h->kmer_size, h->omega, nk, ne);
+                                                        h->newick, h->kmer_size, h->omega, nk, ne, positioned);
     uint64_t total = 0;
     std::vector<uint8_t> ob;
     ob.reserve(OUT_BUF + ((size_t)1 << 20));

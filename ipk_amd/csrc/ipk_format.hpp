@@ -108,9 +108,10 @@ inline bool skip_string(FILE* f, uint64_t limit = (uint64_t)1 << 32)
     uint64_t n = 0;
     return get_v(f, n) && n <= limit && fseek(f, (long)n, SEEK_CUR) == 0;
 }
-// Positions `f` at the first k-mer record; the header's totals come back.  false: not a file of this layout (as written by
+// Positions `f` at the first k-mer record; the header's totals come back, and with positions_loaded the positions flag (false where
+// the layout has none: protocol version 0).  false: not a file of this layout (as written by
 // this process: the protocol word is expected exactly when protocol_version() is non-zero, and must hold that value).
-inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries)
+inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries, bool* positions_loaded = nullptr)
 {
     uint64_t n = 0;
     char magic[22];
@@ -123,6 +124,7 @@ inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries)
     if (proto && (!get_v(f, got) || got != proto)) return false;
     if (!skip_string(f) || (proto && (!get_v(f, positions) || positions > 1)) || !get_v(f, n_index) || n_index > ((uint64_t)1 << 32) || fseek(f, (long)(n_index * 16), SEEK_CUR) != 0) return false;
     if (!skip_string(f) || !get_v(f, kmer_size) || !get_v(f, omega)) return false;
+    if (positions_loaded) *positions_loaded = positions != 0;
     return get_v(f, total_kmers) && get_v(f, total_entries);
 }
 // the order of the k-mer records: ascending filter value (as an order-preserving integer code of the float), ties by

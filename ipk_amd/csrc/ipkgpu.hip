@@ -1925,25 +1925,31 @@ namespace {
 
 // Merges S sources of one owner: source s brings its counts row counts_rows[s] ([slots], device) and its entry block
 // src_rows[s] (device).  Writes dst entries (n_total), dst_off [slots+1] into ctx->tmp_b, and, when `db` is given, the
-// compact key list.
+// compact key list.  pos_rows / pdst_out (both or neither): source s's window starts, aligned with src_rows[s]; they are copied
+// beside the entries in the same pass (merge_copy_pos_kernel) into *pdst_out.  Without them nothing here differs.
 int merge_sources(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t P, uint32_t S, uint64_t slots,
                   const std::vector<const uint32_t*>& counts_rows, const std::vector<const uint2*>& src_rows,
-                  uint32_t* total_out /*[slots] device*/, uint2** dst_out, uint64_t* n_total_out, ipkgpu_db* db)
+                  uint32_t* total_out /*[slots] device*/, uint2** dst_out, uint64_t* n_total_out, ipkgpu_db* db,
+                  const std::vector<const uint32_t*>* pos_rows = nullptr, uint32_t** pdst_out = nullptr)
 {
+    const bool with_pos = pos_rows != nullptr;
+    if (with_pos != (pdst_out != nullptr) || (with_pos && pos_rows->size() != S)) return fail(ctx, IPKGPU_ERR_INVALID, "internal: positions of a merge need sources and a destination");
+    const size_t ptr_bytes = (size_t)S * (with_pos ? 24 : 16);
     // workspaces: tmp_a = flags u32[slots] ; tmp_b = dst_off u64[slots+1] ; tmp_c = ONE scan over the sources' counts rows laid end to
     // end, u64[S * slots + 1] (it was a scan per source: 2 S launches) ; ptrs = the pointer arrays (uploaded from pinned staging: no wait)
     RC_TRY(ensure(ctx, ctx->tmp_a, slots * 4));
     RC_TRY(ensure(ctx, ctx->tmp_b, (slots + 1) * 8));
     RC_TRY(ensure(ctx, ctx->tmp_c, ((size_t)S * slots + 1) * 8));
-    RC_TRY(ensure(ctx, ctx->ptrs, (size_t)S * 16));
+    RC_TRY(ensure(ctx, ctx->ptrs, ptr_bytes));
     void* stage = nullptr;
-    RC_TRY(upload_stage(ctx, (size_t)S * 16, &stage));
+    RC_TRY(upload_stage(ctx, ptr_bytes, &stage));
     const void** hp = reinterpret_cast<const void**>(stage);
-    for (uint32_t s = 0; s < S; ++s) { hp[s] = counts_rows[s]; hp[S + s] = src_rows[s]; }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ptrs.p, hp, (size_t)S * 16, hipMemcpyHostToDevice, ctx->stream));
+    for (uint32_t s = 0; s < S; ++s) { hp[s] = counts_rows[s]; hp[S + s] = src_rows[s]; if (with_pos) hp[2 * (size_t)S + s] = (*pos_rows)[s]; }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ptrs.p, hp, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
     RC_TRY(upload_staged(ctx));
     const uint32_t* const* d_counts = ctx->ptrs.as<const uint32_t*>();
     const uint2* const* d_src = reinterpret_cast<const uint2* const*>(ctx->ptrs.as<const void*>() + S);
+    const uint32_t* const* d_psrc = reinterpret_cast<const uint32_t* const*>(ctx->ptrs.as<const void*>() + 2 * (size_t)S);   // (with_pos only)
     const uint32_t nb256 = (uint32_t)((slots + 255) / 256);
     hipLaunchKernelGGL(merge_sum_counts_kernel, dim3(nb256), dim3(256), 0, ctx->stream, d_counts, S, slots, total_out,
                        ctx->tmp_a.as<uint32_t>());
@@ -1956,12 +1962,21 @@ int merge_sources(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, u
     const uint64_t n_total = h_tot[0];
     uint2* dst = nullptr;
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&dst, std::max<uint64_t>(n_total, 1) * 8));
+    *dst_out = dst;                       // owned by the caller from here on (also on failure)
+    uint32_t* pdst = nullptr;
+    if (with_pos) {
+        HIP_TRY(ctx, ctx_alloc(ctx, (void**)&pdst, std::max<uint64_t>(n_total, 1) * 4));
+        *pdst_out = pdst;                 // (the caller's, like dst)
+    }
     for (uint64_t first = 0; first < slots; first += WAVE_PER_ITEM_SPAN) {   // (a wavefront per slot: 4^13 slots in one launch would be 2^32 threads)
         const uint64_t span = std::min<uint64_t>(WAVE_PER_ITEM_SPAN, slots - first);
-        hipLaunchKernelGGL(merge_copy_kernel, dim3((uint32_t)((span + 3) / 4)), dim3(256), 0, ctx->stream, d_counts, S, slots,
-                           ctx->tmp_c.as<uint64_t>(), d_src, ctx->tmp_b.as<uint64_t>(), dst, first);
+        if (with_pos)
+            hipLaunchKernelGGL(merge_copy_pos_kernel, dim3((uint32_t)((span + 3) / 4)), dim3(256), 0, ctx->stream, d_counts, S, slots,
+                               ctx->tmp_c.as<uint64_t>(), d_src, d_psrc, ctx->tmp_b.as<uint64_t>(), dst, pdst, first);
+        else
+            hipLaunchKernelGGL(merge_copy_kernel, dim3((uint32_t)((span + 3) / 4)), dim3(256), 0, ctx->stream, d_counts, S, slots,
+                               ctx->tmp_c.as<uint64_t>(), d_src, ctx->tmp_b.as<uint64_t>(), dst, first);
     }
-    *dst_out = dst;                       // owned by the caller from here on (also on failure)
     *n_total_out = n_total;
     HIP_TRY(ctx, hipGetLastError());
     if (db) {
@@ -1990,14 +2005,15 @@ int merge_sources(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, u
 
 // The key-major call; lead > 0: the key-range pass of the k-mers whose first `lead` symbols spell lead_c (one owner)
 int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites, uint32_t sigma, const uint32_t* mat_group,
-                  uint32_t k, float log_eps, uint32_t n_owners, uint32_t lead, uint32_t lead_c, ipkgpu_parts** out, bool positions = false)
+                  uint32_t k, float log_eps, uint32_t n_owners, uint32_t lead, uint32_t lead_c, ipkgpu_parts** out, bool positions = false,
+                  bool pos_owners = false)   // (pos_owners: the positioned call that splits by owner and accepts a rank without groups)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (n_owners == 0) return fail(ctx, IPKGPU_ERR_INVALID, "n_owners must be >= 1");
-    if (positions && n_owners != 1) return fail(ctx, IPKGPU_ERR_INVALID, "a positioned database is built for one owner (n_owners = %u): the exchange does not carry positions", n_owners);
-    if (positions && n_mats == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no matrices");
+    if (positions && !pos_owners && n_owners != 1) return fail(ctx, IPKGPU_ERR_INVALID, "a positioned database is built for one owner (n_owners = %u): the exchange does not carry positions", n_owners);
+    if (positions && !pos_owners && n_mats == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no matrices");
     const uint64_t key_base = lead ? (uint64_t)lead_c * ipow(sigma, (int)(k - lead)) : 0;
     if (n_mats == 0) {
         // a rank without branch groups (more ranks than groups): empty parts, so that it still takes part in the exchange
@@ -2011,6 +2027,15 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         struct EGuard { ipkgpu_parts* r; ~EGuard() { if (r) ipkgpu_parts_free(r); } } eg{e};
         HIP_TRY(ctx, ctx_alloc(ctx, (void**)&e->d_counts, (size_t)n_owners * e->slots * 4));
         HIP_TRY(ctx, ctx_alloc(ctx, (void**)&e->d_entries, 8));
+        if (positions) {
+            // an empty positioned piece: it meets the same refusals as one with groups, so that ranks do not disagree on them
+            Geometry geo;
+            RC_TRY(fill_geometry(ctx, sigma, k, 0, geo));
+            if (lead != 0 || geo.xp_nb == 0)
+                return fail(ctx, IPKGPU_ERR_INVALID, "no positioned database for sigma=%u k=%u: the call takes the exact partition, which needs more than 64 keys "
+                                                     "and no key-range pass", sigma, k);
+            HIP_TRY(ctx, ctx_alloc(ctx, (void**)&e->d_positions, 4));
+        }
         HIP_TRY(ctx, hipMemsetAsync(e->d_counts, 0, (size_t)n_owners * e->slots * 4, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         eg.r = nullptr;
@@ -2360,6 +2385,13 @@ int ipkgpu_score_groups_keymajor_positions_device(ipkgpu_ctx* ctx, const float* 
 }
 
 uint64_t ipkgpu_parts_key_base(const ipkgpu_parts* p) { return p ? p->key_base : 0; }
+int ipkgpu_score_groups_keymajor_positions_owners_device(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint32_t sites,
+                                                         uint32_t sigma, const uint32_t* mat_group, uint32_t k, float log_eps,
+                                                         uint32_t n_owners, ipkgpu_parts** out)
+{
+    return keymajor_impl(ctx, logp_dev, n_mats, sites, sigma, mat_group, k, log_eps, n_owners, 0, 0, out, true, true);
+}
+
 const uint32_t* ipkgpu_parts_positions_device(const ipkgpu_parts* p) { return p ? p->d_positions : nullptr; }
 
 uint32_t ipkgpu_parts_num_owners(const ipkgpu_parts* p) { return p ? p->n_owners : 0; }
@@ -2453,6 +2485,40 @@ int ipkgpu_merge_parts_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_
     for (uint32_t s = 0; s < n_sources; ++s) srow[s] = reinterpret_cast<const uint2*>(entries_dev[s]);
     RC_TRY(ensure(ctx, ctx->counts, slots * 4));
     RC_TRY(merge_sources(ctx, sigma, k, owner, n_owners, n_sources, slots, crow, srow, ctx->counts.as<uint32_t>(), &db->d_entries, &db->n_entries, db));
+    const int t1 = sw.mark();
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    db->t_merge = sw.ms(t0, t1);
+    guard.r = nullptr;
+    *out = db;
+    return IPKGPU_OK;
+}
+
+int ipkgpu_merge_parts_positions_ptrs(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, uint32_t n_sources,
+                                      const uint32_t* const* counts_dev, const void* const* entries_dev, const uint32_t* const* positions_dev,
+                                      ipkgpu_db** out)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
+    *out = nullptr;
+    if (!counts_dev || !entries_dev || !positions_dev) return fail(ctx, IPKGPU_ERR_INVALID, "null input pointer");
+    if ((sigma != 4 && sigma != 20) || k < 2 || k > ipkgpu_max_k(sigma)) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
+    if (n_owners == 0 || owner >= n_owners || n_sources == 0) return fail(ctx, IPKGPU_ERR_INVALID, "bad owner/source counts");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t T = ipow(sigma, (int)k);
+    const uint64_t slots = (T + n_owners - 1) / n_owners;
+    ipkgpu_db* db = new (std::nothrow) ipkgpu_db();
+    if (!db) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
+    db->ctx = ctx;
+    struct Guard { ipkgpu_db* r; ~Guard() { if (r) ipkgpu_db_free(r); } } guard{db};
+    Stopwatch sw(ctx->stream, &ctx->events);
+    const int t0 = sw.mark();
+    std::vector<const uint32_t*> crow(counts_dev, counts_dev + n_sources);
+    std::vector<const uint32_t*> prow(positions_dev, positions_dev + n_sources);
+    std::vector<const uint2*> srow(n_sources);
+    for (uint32_t s = 0; s < n_sources; ++s) srow[s] = reinterpret_cast<const uint2*>(entries_dev[s]);
+    RC_TRY(ensure(ctx, ctx->counts, slots * 4));
+    RC_TRY(merge_sources(ctx, sigma, k, owner, n_owners, n_sources, slots, crow, srow, ctx->counts.as<uint32_t>(), &db->d_entries, &db->n_entries, db,
+                         &prow, &db->d_positions));
     const int t1 = sw.mark();
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     db->t_merge = sw.ms(t0, t1);

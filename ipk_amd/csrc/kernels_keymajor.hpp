@@ -973,6 +973,61 @@ __global__ __launch_bounds__(256) void merge_copy_kernel(const uint32_t* const* 
     }
 }
 
+// merge_copy_kernel for positioned sources: psrc[s] = source s's window starts (u32), aligned entry for entry with src[s].  The 8-byte
+// entry and the 4-byte position of an index go to the same destination index of dst / pdst; counts rows and goff are read once for
+// both (lane s fetches source s's count, offset, entry base and position base in one round trip).
+__global__ __launch_bounds__(256) void merge_copy_pos_kernel(const uint32_t* const* __restrict__ counts, uint32_t S, uint64_t slots,
+                                                             const uint64_t* __restrict__ goff,      // [S * slots + 1]
+                                                             const uint2* const* __restrict__ src,
+                                                             const uint32_t* const* __restrict__ psrc,
+                                                             const uint64_t* __restrict__ dst_off,   // [slots+1]
+                                                             uint2* __restrict__ dst, uint32_t* __restrict__ pdst,
+                                                             uint64_t first)
+{
+    const uint64_t q = first + (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= slots) return;
+    const uint32_t lane = lane_id();
+    uint64_t d = dst_off[q];
+    for (uint32_t s0 = 0; s0 < S; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        uint32_t n_s = 0;
+        uint64_t from_s = 0, pfrom_s = 0;
+        if (s < S) {
+            const global_u32_ptr row = (global_u32_ptr)counts[s];
+            n_s = row[q];
+            const uint64_t at = goff[(uint64_t)s * slots + q] - goff[(uint64_t)s * slots];
+            from_s = reinterpret_cast<uint64_t>(src[s]) + 8ull * at;
+            pfrom_s = reinterpret_cast<uint64_t>(psrc[s]) + 4ull * at;
+        }
+        const uint32_t ns = min(64u, S - s0);
+        // four sources per trip: their loads (entry and position) are issued together, then their stores
+        for (uint32_t t0 = 0; t0 < ns; t0 += 4) {
+            typedef const unsigned long long __attribute__((address_space(1)))* global_u64_ptr;   // (an entry as one 64-bit word)
+            unsigned long long* const dst64 = reinterpret_cast<unsigned long long*>(dst);
+            uint32_t n[4]; global_u64_ptr from[4]; global_u32_ptr pfrom[4]; unsigned long long v[4]; uint32_t pv[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                const uint32_t t = min(t0 + u, ns - 1);
+                n[u] = t0 + u < ns ? (uint32_t)__builtin_amdgcn_readlane((int)n_s, (int)t) : 0u;
+                const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)from_s, (int)t);
+                const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(from_s >> 32), (int)t);
+                from[u] = (global_u64_ptr)(((uint64_t)hi << 32) | lo);
+                const uint32_t plo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pfrom_s, (int)t);
+                const uint32_t phi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pfrom_s >> 32), (int)t);
+                pfrom[u] = (global_u32_ptr)(((uint64_t)phi << 32) | plo);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) if (lane < n[u]) { v[u] = from[u][lane]; pv[u] = pfrom[u][lane]; }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                if (lane < n[u]) { dst64[d + lane] = v[u]; pdst[d + lane] = pv[u]; }
+                for (uint32_t i = lane + 64; i < n[u]; i += 64) { dst64[d + i] = from[u][i]; pdst[d + i] = pfrom[u][i]; }   // (rare)
+                d += n[u];
+            }
+        }
+    }
+}
+
 // single source: total = counts, flags = (counts != 0)
 __global__ __launch_bounds__(256) void flags_from_counts_kernel(const uint32_t* __restrict__ counts, uint64_t slots,
                                                                 uint32_t* __restrict__ total, uint32_t* __restrict__ flags)

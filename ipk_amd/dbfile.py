@@ -230,7 +230,9 @@ def splitmix_unit(keys):
 
 def merge_shard_files(path, sequence_type, tree_index, newick, kmer_size, omega, shard_paths):
     """ipkgpu_db_merge_files: streaming P-way merge of the ranks' shard files (each a database file in its own filter order)
-    by (filter value, key) -- merge_stage2's role (db_builder.cpp:392-458).  Returns (total k-mers, total entries)."""
+    by (filter value, key) -- merge_stage2's role (db_builder.cpp:392-458).  Returns (total k-mers, total entries).
+    Positioned shards (write_db_positions / a positioned Db through write_db_device: the positions flag in their headers) give a
+    positioned file; a mixture of positioned and plain shards is refused."""
     L = _lib()
     h = _header(sequence_type, tree_index, newick, kmer_size, omega)
     arr = (C.c_char_p * len(shard_paths))(*[str(p).encode() for p in shard_paths])

@@ -84,21 +84,24 @@ def pieces_model(n_groups, world, entries_per_rank, ms_per_group, call_ms=0.52, 
                             "entries_per_rank": entries_per_rank, "groups_per_rank": n_groups, "world": world}, "by_pieces": out}
 
 
-def exchange_parts(counts, entries, owner_offsets, dist, world):
+def exchange_parts(counts, entries, owner_offsets, dist, world, positions=None):
     """Rehearsal transport (torch.distributed): all-to-all of the per-owner blocks of ONE piece.
 
-    counts   tensor [world, slots] int32 -- row o goes to rank o
-    entries  tensor [n, 2] int32         -- rows owner_offsets[o]:owner_offsets[o+1] go to rank o
-    Returns (recv_counts [world, slots], recv_entries [m, 2], recv sizes per source)."""
+    counts     tensor [world, slots] int32 -- row o goes to rank o
+    entries    tensor [n, 2] int32         -- rows owner_offsets[o]:owner_offsets[o+1] go to rank o
+    positions  tensor [n] int32 or None    -- a positioned piece's window starts: the same rows travel the same way
+    Returns (recv_counts [world, slots], recv_entries [m, 2], recv sizes per source), with positions a fourth element,
+    recv_positions [m], laid out as recv_entries.  Every rank passes positions or none does (the ranks score a piece with the same
+    call); the in-library exchange checks that, this transport would wait in its last all-to-all."""
     import torch
     dev = counts.device
     send_sizes = [int(owner_offsets[o + 1] - owner_offsets[o]) for o in range(world)]
     if world == 1:
-        return counts, entries, send_sizes
+        return (counts, entries, send_sizes) if positions is None else (counts, entries, send_sizes, positions)
     if dev.type == "cuda" and dist.get_backend() == "gloo":
         # gloo has no device all-to-all: stage through host memory
-        rc, re_, rs = exchange_parts(counts.cpu(), entries.cpu(), owner_offsets, dist, world)
-        return rc.to(dev), re_.to(dev), rs
+        got = exchange_parts(counts.cpu(), entries.cpu(), owner_offsets, dist, world, None if positions is None else positions.cpu())
+        return tuple(x.to(dev) if hasattr(x, "to") else x for x in got)
     ss = torch.tensor(send_sizes, dtype=torch.int64, device=dev)
     rs = torch.empty(world, dtype=torch.int64, device=dev)
     dist.all_to_all_single(rs, ss)
@@ -107,7 +110,11 @@ def exchange_parts(counts, entries, owner_offsets, dist, world):
     dist.all_to_all_single(recv_counts, counts.contiguous())
     recv_entries = torch.empty((sum(recv_sizes), 2), dtype=entries.dtype, device=dev)
     dist.all_to_all_single(recv_entries, entries.contiguous(), output_split_sizes=recv_sizes, input_split_sizes=send_sizes)
-    return recv_counts, recv_entries, recv_sizes
+    if positions is None:
+        return recv_counts, recv_entries, recv_sizes
+    recv_positions = torch.empty(sum(recv_sizes), dtype=positions.dtype, device=dev)
+    dist.all_to_all_single(recv_positions, positions.contiguous(), output_split_sizes=recv_sizes, input_split_sizes=send_sizes)
+    return recv_counts, recv_entries, recv_sizes, recv_positions
 
 
 def init_native_comm(engine, dist, world, rank):
@@ -162,9 +169,9 @@ def build_db_shard(engine, logp, mat_group, k, log_eps, sigma, dist=None, world=
     exposed; the merge takes pieces x world sources in the order (rank 0 piece 0, rank 0 piece 1, ..., rank 1 piece 0, ...),
     which is global group order.  All ranks use the same piece count (agree_on_pieces: two small all-reduces per call, unless the
     caller settled the count beforehand -- `pieces` from agree_on_pieces() with agreed=True, as a loop over equally shaped calls does).
-    positions=True (one rank): the positioned database of --keep-positions."""
-    if positions and world != 1:
-        raise ValueError("positions: one rank only (the exchange does not carry positions yet)")
+    positions=True: the positioned database of --keep-positions.  Several ranks score their pieces with
+    score_groups_keymajor_positions_owners; the window starts travel and are merged beside their entries, and the shard has
+    Db.positions()."""
     if world == 1:
         # positions=True: every entry's window start rides along (Db.positions()), one scoring pass all the same
         score = engine.score_groups_keymajor_positions if positions else engine.score_groups_keymajor
@@ -186,25 +193,33 @@ def build_db_shard(engine, logp, mat_group, k, log_eps, sigma, dist=None, world=
     scored, xs = [], []
     for j in range(n):
         a, b = cuts[j], cuts[j + 1]
-        pj = engine.score_groups_keymajor(logp[a:b], mat_group[a:b], k, log_eps, n_owners=world)
+        score = engine.score_groups_keymajor_positions_owners if positions else engine.score_groups_keymajor
+        pj = score(logp[a:b], mat_group[a:b], k, log_eps, n_owners=world)
         scored.append(pj)
         if native:
             xs.append(engine.exchange_begin(pj))                            # enqueued on the communicator's stream: runs under the next piece
         else:
-            xs.append(exchange_parts(pj.counts_tensor(), pj.entries_tensor(), pj.owner_offsets, dist, world))
+            xs.append(exchange_parts(pj.counts_tensor(), pj.entries_tensor(), pj.owner_offsets, dist, world,
+                                     pj.positions_tensor() if positions else None))
     t_wait = time.perf_counter()
     if native:
         db, exposed = engine.exchange_merge(xs, sigma, k)
     else:
         torch.cuda.current_stream().synchronize()
         # sources in global group order: (rank s, piece 0), (rank s, piece 1), ...: one pointer pair per source
-        cps, eps = [], []
+        cps, eps, pps = [], [], []
         for s in range(world):
-            for rc, re_, rs in xs:
+            for got in xs:
+                rc, re_, rs = got[:3]
                 cps.append(rc[s].data_ptr())
                 off = int(sum(rs[:s]))
                 eps.append(re_.data_ptr() + 8 * off)
-        db = engine.merge_parts_ptrs(sigma, k, rank, world, cps, eps)
+                if positions:
+                    pps.append(got[3].data_ptr() + 4 * off)
+        if positions:
+            db = engine.merge_parts_positions_ptrs(sigma, k, rank, world, cps, eps, pps)
+        else:
+            db = engine.merge_parts_ptrs(sigma, k, rank, world, cps, eps)
         exposed = (time.perf_counter() - t_wait) * 1e3
     first = scored[0]
     first.exchange_exposed_ms = exposed

@@ -316,6 +316,8 @@ def _bind_keymajor(L):
                                                       C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.ipkgpu_score_groups_keymajor_positions_device.restype = C.c_int
     L.ipkgpu_score_groups_keymajor_positions_device.argtypes = L.ipkgpu_score_groups_keymajor_device.argtypes
+    L.ipkgpu_score_groups_keymajor_positions_owners_device.restype = C.c_int
+    L.ipkgpu_score_groups_keymajor_positions_owners_device.argtypes = L.ipkgpu_score_groups_keymajor_device.argtypes
     L.ipkgpu_parts_positions_device.restype = C.c_void_p
     L.ipkgpu_parts_positions_device.argtypes = [C.c_void_p]
     L.ipkgpu_db_positions.restype = u32p
@@ -346,6 +348,8 @@ def _bind_keymajor(L):
     L.ipkgpu_merge_parts_ptrs.restype = C.c_int
     L.ipkgpu_merge_parts_ptrs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.ipkgpu_merge_parts_positions_ptrs.restype = C.c_int
+    L.ipkgpu_merge_parts_positions_ptrs.argtypes = L.ipkgpu_merge_parts_ptrs.argtypes[:-1] + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.ipkgpu_comm_unique_id.restype = C.c_int
     L.ipkgpu_comm_unique_id.argtypes = [C.c_void_p]
     L.ipkgpu_comm_init.restype = C.c_int
@@ -419,6 +423,7 @@ ABI_SYMBOLS += [
     "ipkgpu_max_k_keyrange", "ipkgpu_score_groups_keyrange_device", "ipkgpu_parts_key_base",
     "ipkgpu_score_groups_keymajor_positions_device", "ipkgpu_parts_positions_device", "ipkgpu_db_positions",
     "ipkgpu_db_positions_device",
+    "ipkgpu_score_groups_keymajor_positions_owners_device", "ipkgpu_merge_parts_positions_ptrs",
 ]
 
 
@@ -583,7 +588,7 @@ def _device_tensor(ptr, shape, dtype, owner):
 
 
 def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None, keyrange=None,
-                           positions=False):
+                           positions=False, owners=False):
     """Scoring pass with key-major, owner-split output (see include/ipkgpu.h). logp: torch CUDA tensor
     [n_mats, sites, sigma] float32 or a raw device pointer with explicit shape.  keyrange = (lead, cls): the key-range pass of
     the k-mers whose first `lead` symbols spell `cls` (one owner; ipkgpu_score_groups_keyrange_device)."""
@@ -612,7 +617,8 @@ def _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=1, sigma=
                                                            mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
                                                            C.c_float(log_eps), lead, cls, C.byref(out))
     elif positions:
-        rc = self._lib.ipkgpu_score_groups_keymajor_positions_device(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
+        call = self._lib.ipkgpu_score_groups_keymajor_positions_owners_device if owners else self._lib.ipkgpu_score_groups_keymajor_positions_device
+        rc = call(self._h, C.c_void_p(ptr), n_mats, sites, sigma,
                                                                      mat_group.ctypes.data_as(C.POINTER(C.c_uint32)), k,
                                                                      C.c_float(log_eps), n_owners, C.byref(out))
     else:
@@ -653,6 +659,23 @@ def _merge_parts_ptrs(self, sigma, k, owner, n_owners, counts_ptrs, entries_ptrs
     return self._adopt(Db(self._lib, out))
 
 
+def _merge_parts_positions_ptrs(self, sigma, k, owner, n_owners, counts_ptrs, entries_ptrs, positions_ptrs):
+    """merge_parts_ptrs over positioned sources: one (counts row, entry block, window starts) device pointer triple per source, in
+    source order; the Db has positions()."""
+    _bind_keymajor(self._lib)
+    n = len(counts_ptrs)
+    if len(entries_ptrs) != n or len(positions_ptrs) != n:
+        raise ValueError("one counts, entries and positions pointer per source")
+    cp = (C.c_void_p * n)(*[int(x) for x in counts_ptrs])
+    ep = (C.c_void_p * n)(*[int(x) for x in entries_ptrs])
+    pp = (C.c_void_p * n)(*[int(x) for x in positions_ptrs])
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_merge_parts_positions_ptrs(self._h, sigma, k, owner, n_owners, n, cp, ep, pp, C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return self._adopt(Db(self._lib, out))
+
+
 def _comm_unique_id(self):
     _bind_keymajor(self._lib)
     buf = (C.c_uint8 * 128)()
@@ -688,6 +711,7 @@ def _comm_init(self, unique_id, rank, world):
 
 
 def _exchange_begin(self, parts):
+    """Enqueues block o -> rank o of one piece; positioned parts send their window starts beside the entries."""
     out = C.c_void_p()
     rc = self._lib.ipkgpu_exchange_begin(self._h, parts._h, C.byref(out))
     if rc != 0:
@@ -696,7 +720,8 @@ def _exchange_begin(self, parts):
 
 
 def _exchange_merge(self, xfers, sigma, k):
-    """-> (Db, exposed transfer time in ms); frees the transfer handles."""
+    """-> (Db, exposed transfer time in ms); frees the transfer handles.  All pieces positioned: the Db has positions(); a mixture of
+    positioned and plain pieces is refused."""
     n = len(xfers)
     arr = (C.c_void_p * n)(*[x.value for x in xfers])
     out = C.c_void_p()
@@ -722,6 +747,7 @@ def _db_from_parts(self, parts, sigma, k):
 
 Engine.db_from_parts = _db_from_parts
 Engine.merge_parts_ptrs = _merge_parts_ptrs
+Engine.merge_parts_positions_ptrs = _merge_parts_positions_ptrs
 Engine.comm_unique_id = _comm_unique_id
 Engine.comm_init = _comm_init
 Engine.comm_prepare = _comm_prepare
@@ -750,4 +776,14 @@ def _score_groups_keymajor_positions(self, logp, mat_group, k, log_eps, n_owners
 
 
 Engine.score_groups_keymajor_positions = _score_groups_keymajor_positions
+
+
+def _score_groups_keymajor_positions_owners(self, logp, mat_group, k, log_eps, n_owners=1, sigma=None, sites=None, n_mats=None):
+    """score_groups_keymajor_positions split by owner (include/ipkgpu.h, ipkgpu_score_groups_keymajor_positions_owners_device): any
+    n_owners >= 1, block o of Parts.positions_tensor() beside block o of the entries; no matrices give empty positioned parts."""
+    return _score_groups_keymajor(self, logp, mat_group, k, log_eps, n_owners=n_owners, sigma=sigma, sites=sites, n_mats=n_mats,
+                                  positions=True, owners=True)
+
+
+Engine.score_groups_keymajor_positions_owners = _score_groups_keymajor_positions_owners
 Engine.merge_parts = _merge_parts
