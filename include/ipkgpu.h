@@ -30,9 +30,8 @@
  * through the per-branch result or the positions path, not for amino acids k = 7 (35-bit keys).  At DNA k >= 13 also
  * a call in which one window's half list (its 6- to 8-symbol prefixes or suffixes above their threshold) exceeds 6144
  * entries, by every scoring entry point, ipkgpu_score_groups_positions included: near-uniform columns, which real
- * posteriors do not have -- and the reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group
- * files merged later): groups are batched by device memory instead ("workspace_bytes") and the k-mer-keyed
- * merge of batches / ranks runs on the device (ipkgpu_merge_parts*).
+ * posteriors do not have.  The reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group files
+ * merged later) is ipkgpu_parts_spill / ipkgpu_spill_merge below: one GPU, no positions, no key-range passes.
  */
 #ifndef IPKGPU_H
 #define IPKGPU_H
@@ -105,7 +104,9 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * table slices reduced by the workgroup-per-slice kernel instead of the persistent one; 12 / 13: the compressed key-major writer
  * per key block / per run of key blocks whatever the group count), "debug_pool_chunks", "debug_pool_limit_bytes",
  * "debug_wg_chunks2", "debug_rounds", "debug_kmc_pass" (groups per pass of the compressed key-major writer),
- * "debug_prefix_mats" (matrices per workgroup of the prefix-sum kernel: 1, 2, 4, 8; 0 = by the matrix count) (diagnostics and tests only).
+ * "debug_prefix_mats" (matrices per workgroup of the prefix-sum kernel: 1, 2, 4, 8; 0 = by the matrix count) (diagnostics and tests only);
+ * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "release_workspaces" (any value: the context's workspaces and cached result
+ * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
  * Every variant yields identical results.  Returns IPKGPU_ERR_INVALID for unknown names.
  *
  * Calls on one context are synchronous, but from its second scoring call on a context waits on its stream ONCE per key-major
@@ -321,6 +322,33 @@ int ipkgpu_exchange_merge(ipkgpu_ctx* ctx, ipkgpu_xfer* const* xfers, uint32_t n
                           double* exposed_ms /* optional: time spent waiting for transfers */);
 double ipkgpu_xfer_exposed_ms(const ipkgpu_xfer* x);
 void ipkgpu_xfer_free(ipkgpu_xfer* x);
+
+/* ---- the on-disk build: a database larger than device memory (db_builder.cpp:137,340-458,673-681; branch_group.cpp:104-185) ----
+ * Stage 1: the groups are scored in pieces (contiguous ranges of the first-seen group order), each with
+ * ipkgpu_score_groups_keymajor_device(..., n_owners = B); ipkgpu_parts_spill takes the piece's B owner blocks off the device, one file
+ * `dir`/p<piece>_b<owner>.blk each (layout: ipk_amd/csrc/spill_format.hpp -- occupancy bits of the counts row, the non-empty slots'
+ * counts as u16, the entries unchanged; an empty block is written too: head and zero bits).  Stage 2, per batch b: ipkgpu_spill_merge reads the
+ * pieces' blocks of owner b IN THE ORDER GIVEN (piece order = group order = the reference's append order), unpacks them and merges them as
+ * ipkgpu_merge_parts does; the database is filtered and written like any other, its file merged with the other batches' by
+ * ipkgpu_db_merge_files.  The device never holds more than one piece's result or one batch of the database.
+ * ipkgpu_parts_spill refuses (IPKGPU_ERR_INVALID) positioned parts (the reference keeps no positions on disk either, db_builder.cpp:469),
+ * key-range parts, and a piece in which a key has more than 65535 entries (more groups than that in one piece); a failed write leaves no
+ * file under a block's final name.  ipkgpu_spill_merge checks every block on the host before anything is launched -- the head (magic, version,
+ * sigma, k, n_owners, owner, slots, the file size against its totals), then the body against the head as it is read -- and names the file it
+ * refuses; the head checks need no context (ctx == NULL: the message is ipkgpu_last_error(NULL)'s, the status IPKGPU_ERR_INVALID in any case). */
+int ipkgpu_parts_spill(ipkgpu_ctx* ctx, ipkgpu_parts* parts, const char* dir, uint32_t piece, uint64_t* bytes_written);
+int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, const char* const* block_paths,
+                       uint32_t n_blocks, ipkgpu_db** out);
+/* Device memory the context holds from hipMalloc -- its workspaces and its result blocks, live or cached -- and the high-water mark of
+ * that figure (reset_peak != 0: the mark restarts from the current figure after it has been reported).  Option "device_budget_bytes"
+ * (0 = none, the default) makes the context behave like a device of that size: an allocation that would take the figure beyond the budget
+ * first drops the cached blocks and, if it still would, fails with IPKGPU_ERR_NOMEM; work sized by free device memory sees at most what
+ * the budget leaves.  The context stays usable after such a failure.  Device memory of the caller (the matrices) is not counted. */
+int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak);
+/* Reads back "workspace_bytes" or "device_budget_bytes" (a caller that sets them for a while restores them), or "last_refused_bytes":
+ * the bytes held plus the size of the last allocation the device or the budget refused -- what the failed step needed at least.
+ * IPKGPU_ERR_INVALID for other names. */
+int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value);
 
 /* Single-GPU shortcut (n_owners == 1): the parts already ARE the database; produces the key list and
  * MOVES the entry array out of `parts` (which stays valid for its counts/timings, entries become NULL).

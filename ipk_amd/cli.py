@@ -67,7 +67,11 @@ def ipk():
               help="host threads of the probability loader [0 = every core this process may run on, divided among the ranks of a node; the reference's --threads only "
                    "feeds the AR tool (ar.cpp:669,749), which this command does not run]")
 @click.option("-o", "--output", default=None, help="output file [workdir/DB.ipk]")
-@click.option("--on-disk", is_flag=True, help="(ignored: the GPU build batches groups by HBM instead)")
+@click.option("--on-disk", is_flag=True,
+              help="build a database that does not fit device memory: the groups are scored in pieces, every piece's result leaves the device "
+                   "split into 32 k-mer-keyed batches under workdir/hashmaps, and the batches are merged, filtered and written one at a time "
+                   "(db_builder.cpp:340-458); same file as the default build, slower, bound by the file system; one GPU, no --keep-positions, "
+                   "k <= 14 (amino acids 6)")
 @click.option("--mapping", type=click.Path(exists=True), default=None,
               help="TSV: AR node label <TAB> branch post-order id, one line per ghost node (instead of the tree-derived plan)")
 @click.option("--num-tree-nodes", type=int, default=0, help="node count of the original tree (MIF0's N, db_builder.cpp:261); default: the reference tree's, or branch groups + 1 with --mapping")
@@ -80,7 +84,7 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
           ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device, key_passes):
     """Computes a database of phylo-k-mers from precomputed ancestral probabilities."""
     import ipk_amd
-    from ipk_amd import dbfile, distributed, keyrange
+    from ipk_amd import dbfile, distributed, keyrange, ondisk
     from ipk_amd.loader import AncestralProbs
 
     if keep_positions and states == "nucl":
@@ -100,6 +104,12 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
             keyrange.plan(sigma, k, key_passes)
         except ValueError as e:
             raise click.UsageError(f"--key-passes: {e}")
+    if on_disk and keep_positions:
+        raise click.UsageError("--on-disk does not keep positions (neither does the reference, db_builder.cpp:469): drop --keep-positions or --on-disk")
+    if on_disk and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("--on-disk runs on ONE GPU: the batches inside a rank's shard would need a slot mapping of their own (not built)")
+    if on_disk and use_passes:
+        raise click.UsageError(f"--on-disk is not combined with key-range passes (k = {k} / --key-passes): a pass already bounds device memory")
     os.makedirs(workdir, exist_ok=True)
     output = output or os.path.join(workdir, "DB.ipk")
 
@@ -187,6 +197,21 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
             click.echo(f"Filtering time: {kr['filter_s'] * 1e3:.0f} ms ({n} key-range passes)")
             click.echo(f"Merge time: {(kr['write_s'] + kr['merge_s']) * 1e3:.0f} ms ({n} pass files written and merged)")
             click.echo(f"Output: {output} ({kr['totals'][0]} k-mers, {kr['totals'][1]} entries)")
+        eng.close(); arp.close()
+        return
+    if on_disk:
+        n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
+        od = ondisk.build_db_file(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, output, workdir,
+                                  "DNA" if sigma == 4 else "AA", tree_index, newick, omega, filter_, n_nodes)
+        if verbosity:
+            # the reference's three stage timers (db_builder.cpp:236,290,336) over the on-disk build's three stages
+            click.echo(f"Loaded {len(labels)} node matrices ({arp.sites} sites) in {t_load * 1e3:.0f} ms")
+            click.echo(f"Computation time: {od['stage1_s'] * 1e3:.0f} ms ({od['emitted']} scored phylo-k-mers; {od['pieces']} pieces of groups spilled "
+                       f"in {od['batches']} batches, {od['spilled_bytes']} bytes)")
+            click.echo(f"Filtering time: {od['stage2_s'] * 1e3:.0f} ms ({od['batches']} batches merged, filtered and written; device memory held: "
+                       f"at most {od['held_peak']} of {od['budget_bytes']} bytes)")
+            click.echo(f"Merge time: {od['stage3_s'] * 1e3:.0f} ms ({od['batches']} batch files merged)")
+            click.echo(f"Output: {output} ({od['totals'][0]} k-mers, {od['totals'][1]} entries)")
         eng.close(); arp.close()
         return
     t0 = time.time()

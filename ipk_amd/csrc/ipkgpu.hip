@@ -40,6 +40,9 @@
 #include "kernels_reduce_pipe.hpp"
 #include "kernels_filter.hpp"
 #include "kernels_dbfile.hpp"
+#include "kernels_spill.hpp"
+#include "spill_format.hpp"
+#include <sys/stat.h>
 #include <chrono>
 
 using namespace ipkgpu;
@@ -112,6 +115,13 @@ struct ipkgpu_ctx {
     DevBuf table, best, ovfq, counts, offsets, goff, idx, branch, scan_sums, scan_boff, tmp_a, tmp_b, tmp_c;
     DevBuf pool, desc, gbcnt, gboff, gbcur, clist, gm, tile_next;   // stream variant: pair pool, chunk descriptors, chunk index, tile counters
     DevBuf ptrs;                 // per-source pointer arrays of a merge
+    DevBuf sp_bits, sp_pops, sp_rank, sp_c16;   // spill blocks (kernels_spill.hpp): occupancy words, their popcounts and ranks, the u16 counts
+    void* h_spill[2] = {nullptr, nullptr}; hipEvent_t ev_spill[2] = {nullptr, nullptr}; size_t h_spill_cap = 0;   // their pinned staging
+    // bytes this context holds from hipMalloc through dev_malloc (ensure workspaces, result blocks live or cached), their high-water
+    // mark, and option "device_budget_bytes" (0 = none): with one, the context behaves like a device of that size
+    size_t held = 0, held_peak = 0;
+    int64_t budget = 0;
+    size_t refused_need = 0;            // held + size of the last allocation that was refused: what that step needed at least
     DevBuf mask;                 // occupancy bits of ctx->table ([groups in batch][mask_words]) when mask_valid
     bool mask_valid = false;
     uint64_t mask_words = 0;     // 2 * ceil(table_size / 64): rows padded to whole 64-slot blocks
@@ -187,6 +197,7 @@ struct ipkgpu_parts {
     // one owner, one batch: the database's key list (the non-empty slots and their entry offsets) is built inside the scoring
     // call, ahead of the key-major writer -- ipkgpu_db_from_parts then only hands the arrays over
     uint32_t* pre_keys = nullptr; uint64_t* pre_key_off = nullptr; uint64_t pre_n_keys = 0; double t_keys = 0;
+    uint32_t sigma = 0, k = 0;                // of the call that produced the parts
     uint32_t lead = 0;                        // key-range parts (ipkgpu_score_groups_keyrange_device): slot q stands for key key_base + q
     uint64_t key_base = 0;
     double t_total = 0, t_prefix = 0, t_score = 0, t_compact = 0, t_main = 0, t_reduce = 0, t_count = 0, t_write = 0, t_km = 0;
@@ -244,6 +255,40 @@ static int fail(ipkgpu_ctx* ctx, int code, const char* fmt, ...)
     } while (0)
 #define RC_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
+// ---- the one pair of calls through which the context takes and returns device memory ---------------------------------
+// (ensure's workspaces and ctx_alloc's result blocks: `held` counts their bytes.  With a budget, an allocation that would take
+//  `held` beyond it first drops the cached result blocks and, if it still would, fails as a full device does.)
+static hipError_t dev_free(ipkgpu_ctx* ctx, void* p, size_t bytes)
+{
+    const hipError_t e = hipFree(p);
+    ctx->held -= std::min(ctx->held, bytes);
+    return e;
+}
+static void drop_cache(ipkgpu_ctx* ctx)
+{
+    for (auto& b : ctx->free_blocks) (void)dev_free(ctx, b.first, b.second);
+    ctx->free_blocks.clear(); ctx->cached_bytes = 0;
+}
+static hipError_t dev_malloc(ipkgpu_ctx* ctx, void** out, size_t bytes)
+{
+    if (ctx->budget > 0 && ctx->held + bytes > (size_t)ctx->budget) {
+        if (!ctx->free_blocks.empty()) drop_cache(ctx);
+        if (ctx->held + bytes > (size_t)ctx->budget) { ctx->refused_need = ctx->held + bytes; *out = nullptr; return hipErrorOutOfMemory; }
+    }
+    const hipError_t e = hipMalloc(out, bytes);
+    if (e == hipSuccess) { ctx->held += bytes; ctx->held_peak = std::max(ctx->held_peak, ctx->held); }
+    else ctx->refused_need = ctx->held + bytes;
+    return e;
+}
+// free device memory as the context may count on it: the device's, under a budget at most what the budget leaves
+static size_t mem_free_bytes(ipkgpu_ctx* ctx)
+{
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if (ctx->budget > 0) free_b = std::min<size_t>(free_b, (size_t)ctx->budget > ctx->held ? (size_t)ctx->budget - ctx->held : 0);
+    return free_b;
+}
+
 // A workspace of at least `need` bytes.  One that has to GROW gets a sixteenth more than asked for: several sizes follow counts that vary a little
 // from call to call (chunks drawn, values per slice), and a buffer grown to the byte paid hipFree + hipMalloc of the whole block whenever the next
 // call needed one chunk more -- 1.2 s of a 0.1-s step for the 30-GB buffers of all of cfg3 on one GPU (tools/step_trace.py cfg3 1000).
@@ -251,11 +296,11 @@ static int ensure(ipkgpu_ctx* ctx, DevBuf& b, size_t need)
 {
     if (b.cap >= need && b.p) return IPKGPU_OK;
     const bool regrow = b.p != nullptr;
-    if (b.p) { HIP_TRY(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    if (b.p) { HIP_TRY(ctx, dev_free(ctx, b.p, b.cap)); b.p = nullptr; b.cap = 0; }
     need = std::max<size_t>(need, 16);
     size_t want = regrow ? need + need / 16 : need;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess && want > need) { (void)hipGetLastError(); want = need; e = hipMalloc(&b.p, want); }   // (no room for the margin)
+    hipError_t e = dev_malloc(ctx, &b.p, want);
+    if (e != hipSuccess && want > need) { (void)hipGetLastError(); want = need; e = dev_malloc(ctx, &b.p, want); }   // (no room for the margin)
     HIP_TRY(ctx, e);
     b.cap = want;
     return IPKGPU_OK;
@@ -299,12 +344,11 @@ static hipError_t ctx_alloc(ipkgpu_ctx* ctx, void** out, size_t bytes)
         ctx->free_blocks.erase(ctx->free_blocks.begin() + best);
         return hipSuccess;
     }
-    hipError_t e = hipMalloc(out, bytes);
+    hipError_t e = dev_malloc(ctx, out, bytes);
     if (e != hipSuccess && !ctx->free_blocks.empty()) {          // out of memory: drop the cache and retry
-        for (auto& b : ctx->free_blocks) (void)hipFree(b.first);
-        ctx->free_blocks.clear(); ctx->cached_bytes = 0;
+        drop_cache(ctx);
         (void)hipGetLastError();
-        e = hipMalloc(out, bytes);
+        e = dev_malloc(ctx, out, bytes);
     }
     if (e == hipSuccess) ctx->live_blocks[*out] = bytes;
     return e;
@@ -317,7 +361,7 @@ static void ctx_release(ipkgpu_ctx* ctx, void* p)
     const size_t cap = it->second;
     ctx->live_blocks.erase(it);
     if (ctx->cached_bytes + cap <= ctx->cache_limit) { ctx->free_blocks.push_back({p, cap}); ctx->cached_bytes += cap; }
-    else (void)hipFree(p);
+    else (void)dev_free(ctx, p, cap);
 }
 
 // Kernels that give a slot (or a key) a whole wavefront are launched over at most this many items at a time: a HIP launch takes fewer than
@@ -346,6 +390,17 @@ static hipError_t ctx_alloc_atleast(ipkgpu_ctx* ctx, void** out, size_t min_byte
     const hipError_t e = ctx_alloc(ctx, out, want_bytes);
     if (e == hipSuccess) *got = ctx->live_blocks[*out];
     return e;
+}
+
+// every grow-only workspace of a context
+static std::vector<DevBuf*> all_workspaces(ipkgpu_ctx* ctx)
+{
+    return {&ctx->table, &ctx->best, &ctx->ovfq, &ctx->counts, &ctx->offsets, &ctx->goff, &ctx->idx,
+            &ctx->branch, &ctx->scan_sums, &ctx->scan_boff, &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c,
+            &ctx->pool, &ctx->desc, &ctx->gbcnt, &ctx->gboff, &ctx->gbcur, &ctx->clist, &ctx->gm, &ctx->tile_next, &ctx->mask,
+            &ctx->rank, &ctx->vaddr, &ctx->ucnt, &ctx->qpack, &ctx->xstart, &ctx->pcounts, &ctx->ptrs,
+            &ctx->cvals, &ctx->coff, &ctx->croom, &ctx->seq, &ctx->pvals, &ctx->pvaddr, &ctx->mrank, &ctx->cursnap,
+            &ctx->sp_bits, &ctx->sp_pops, &ctx->sp_rank, &ctx->sp_c16};
 }
 
 extern "C" {
@@ -407,16 +462,12 @@ void ipkgpu_destroy(ipkgpu_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* bufs[] = {&ctx->table, &ctx->best, &ctx->ovfq, &ctx->counts, &ctx->offsets, &ctx->goff, &ctx->idx,
-                      &ctx->branch, &ctx->scan_sums, &ctx->scan_boff, &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c,
-                      &ctx->pool, &ctx->desc, &ctx->gbcnt, &ctx->gboff, &ctx->gbcur, &ctx->clist, &ctx->gm, &ctx->tile_next, &ctx->mask,
-                      &ctx->rank, &ctx->vaddr, &ctx->ucnt, &ctx->qpack, &ctx->xstart, &ctx->pcounts, &ctx->ptrs,
-                      &ctx->cvals, &ctx->coff, &ctx->croom, &ctx->seq, &ctx->pvals, &ctx->pvaddr, &ctx->mrank, &ctx->cursnap};
-    for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : all_workspaces(ctx)) if (b->p) (void)hipFree(b->p);
     for (auto& b : ctx->free_blocks) (void)hipFree(b.first);
     ipkgpu_comm_release(ctx);
     if (ctx->small) (void)hipFree(ctx->small);
     if (ctx->h_up) (void)hipHostFree(ctx->h_up);
+    for (int i = 0; i < 2; ++i) { if (ctx->h_spill[i]) (void)hipHostFree(ctx->h_spill[i]); if (ctx->ev_spill[i]) (void)hipEventDestroy(ctx->ev_spill[i]); }
     ctx->pend.sw.reset();
     for (hipEvent_t e : ctx->events.free_ev) (void)hipEventDestroy(e);
     ctx->events.free_ev.clear();
@@ -432,6 +483,22 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
     if (!strcmp(name, "workspace_bytes")) {
         if (value <= 0) return fail(ctx, IPKGPU_ERR_INVALID, "workspace_bytes must be positive");
         ctx->workspace_bytes = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "device_budget_bytes")) {
+        if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "device_budget_bytes must not be negative (0 = no budget)");
+        ctx->budget = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "release_workspaces")) {
+        // between the stages of the on-disk build: the scoring workspaces and the cached result blocks go back to the device (every
+        // call sizes its workspaces anew; blocks of live results stay)
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->up_pending = false;
+        for (DevBuf* b : all_workspaces(ctx)) if (b->p) { (void)dev_free(ctx, b->p, b->cap); b->p = nullptr; b->cap = 0; }
+        drop_cache(ctx);
+        ctx->mask_valid = false; ctx->pend.active = false; ctx->pend.sw.reset();
         return IPKGPU_OK;
     }
     if (!strcmp(name, "variant")) { ctx->opt_variant = value; return IPKGPU_OK; }
@@ -1087,8 +1154,7 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->gboff.as<uint64_t>() + n_units, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     {
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
+        const size_t free_b = mem_free_bytes(ctx);
         const bool over_limit = ctx->opt_pool_limit > 0 && total * 8 > (uint64_t)ctx->opt_pool_limit;
         const uint64_t side = seq ? total * 8 + 512 : 0;          // sequence numbers and position values, 4 bytes per pair each
         const uint64_t side_have = seq ? ctx->seq.cap + ctx->pvals.cap : 0;
@@ -1391,8 +1457,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     const uint64_t n_waves = (uint64_t)n_wg * SNW;
     const uint64_t n_gb = (uint64_t)gb * NBK;
 
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
+    const size_t free_b = mem_free_bytes(ctx);
     uint64_t max_chunks = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)(free_b + ctx->pool.cap + ctx->desc.cap) * 9 / 10 / (CH * 8 + 8));
     if (ctx->opt_pool_limit > 0) max_chunks = std::min<uint64_t>(max_chunks, (uint64_t)ctx->opt_pool_limit / (CH * 8 + 8));
     // pool size: pairs expected (calibrated by the previous call, +25 %) plus every wave's open chunks and id batches.
@@ -2022,7 +2087,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
         ipkgpu_parts* e = new (std::nothrow) ipkgpu_parts();
         if (!e) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
         e->ctx = ctx; e->n_owners = n_owners; e->slots = (ipow(sigma, (int)(k - lead)) + n_owners - 1) / n_owners;
-        e->lead = lead; e->key_base = key_base;
+        e->lead = lead; e->key_base = key_base; e->sigma = sigma; e->k = k;
         e->owner_off.assign((size_t)n_owners + 1, 0);
         struct EGuard { ipkgpu_parts* r; ~EGuard() { if (r) ipkgpu_parts_free(r); } } eg{e};
         HIP_TRY(ctx, ctx_alloc(ctx, (void**)&e->d_counts, (size_t)n_owners * e->slots * 4));
@@ -2063,7 +2128,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
     ipkgpu_parts* parts = new (std::nothrow) ipkgpu_parts();
     if (!parts) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
     parts->ctx = ctx; parts->n_owners = P; parts->slots = slots;
-    parts->lead = lead; parts->key_base = key_base;
+    parts->lead = lead; parts->key_base = key_base; parts->sigma = sigma; parts->k = k;
     parts->owner_off.assign((size_t)P + 1, 0);
     struct Guard { ipkgpu_parts* r; ~Guard() { if (r) ipkgpu_parts_free(r); } } guard{parts};
 
@@ -2929,6 +2994,292 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
     { const auto t0 = std::chrono::steady_clock::now(); const int rc = fclose(out.f); out.f = nullptr; if (rc != 0) return fail(ctx, IPKGPU_ERR_INVALID, "close failed"); t_file += since(t0); }
     ctx->t_write_total = since(t_begin); ctx->t_write_device = t_dev; ctx->t_write_file = t_file;
     if (bytes_written) *bytes_written = total;
+    return IPKGPU_OK;
+}
+
+}  // extern "C"
+
+// ---- spill blocks: a piece's owner blocks off the device, one batch's blocks back (the on-disk build) -------------------------------
+namespace {
+
+constexpr size_t SPILL_STAGE = (size_t)64 << 20;          // bytes of each of the two pinned staging buffers
+
+// the context's two pinned staging buffers of at least `want` bytes each (at most SPILL_STAGE; kept for the next call)
+int spill_stage(ipkgpu_ctx* ctx, size_t want)
+{
+    want = std::min(std::max<size_t>(want, 1 << 16), SPILL_STAGE);
+    for (int i = 0; i < 2; ++i)
+        if (!ctx->ev_spill[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_spill[i], hipEventDisableTiming));
+    if (ctx->h_spill_cap >= want) return IPKGPU_OK;
+    for (int i = 0; i < 2; ++i) { if (ctx->h_spill[i]) (void)hipHostFree(ctx->h_spill[i]); ctx->h_spill[i] = nullptr; }
+    ctx->h_spill_cap = 0;
+    for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipHostMalloc(&ctx->h_spill[i], want, hipHostMallocDefault));
+    ctx->h_spill_cap = want;
+    return IPKGPU_OK;
+}
+
+// one part of a block's byte stream: host bytes (src), device bytes (dev), or zeros (neither)
+struct SpillSeg { uint64_t at, bytes; const void* src; const void* dev; };
+
+std::string spill_block_path(const char* dir, uint32_t piece, uint32_t owner)
+{
+    char name[64];
+    snprintf(name, sizeof name, "/p%u_b%u.blk", piece, owner);
+    return std::string(dir) + name;
+}
+
+struct SpillFile {                      // one input block of ipkgpu_spill_merge, its head checked
+    std::string path; ipkspill::Head head; uint64_t key_base = 0, entry_base = 0;
+};
+
+// Opens and checks every block's head on the host.  ctx may be null (the message then goes where ipkgpu_create's go).
+int spill_check_files(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, const char* const* paths, uint32_t n_blocks,
+                      uint64_t slots, std::vector<SpillFile>& files)
+{
+    files.resize(n_blocks);
+    uint64_t keys = 0, entries = 0;
+    for (uint32_t s = 0; s < n_blocks; ++s) {
+        if (!paths[s]) return fail(ctx, IPKGPU_ERR_INVALID, "null path of block %u", s);
+        SpillFile& f = files[s];
+        f.path = paths[s];
+        FILE* fh = fopen(paths[s], "rb");
+        if (!fh) return fail(ctx, IPKGPU_ERR_INVALID, "cannot open spill block %s", paths[s]);
+        struct stat st;
+        const bool stat_ok = fstat(fileno(fh), &st) == 0;
+        memset(&f.head, 0, sizeof f.head);
+        const size_t got = fread(&f.head, 1, sizeof f.head, fh);
+        fclose(fh);
+        if (!stat_ok) return fail(ctx, IPKGPU_ERR_INVALID, "cannot stat spill block %s", paths[s]);
+        const char* what = got < sizeof f.head ? "shorter than a block's head"
+                                               : ipkspill::check_head(f.head, (uint64_t)st.st_size, sigma, k, n_owners, owner, slots);
+        if (what) return fail(ctx, IPKGPU_ERR_INVALID, "spill block %s: %s", paths[s], what);
+        f.key_base = keys; f.entry_base = entries;
+        keys += f.head.n_keys; entries += f.head.n_entries;
+    }
+    return IPKGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
+{
+    if (!ctx || !name || !value) return IPKGPU_ERR_INVALID;
+    if (!strcmp(name, "workspace_bytes")) { *value = ctx->workspace_bytes; return IPKGPU_OK; }
+    if (!strcmp(name, "device_budget_bytes")) { *value = ctx->budget; return IPKGPU_OK; }
+    if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
+    return IPKGPU_ERR_INVALID;
+}
+
+int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (held) *held = ctx->held;
+    if (held_peak) *held_peak = ctx->held_peak;
+    if (reset_peak) ctx->held_peak = ctx->held;
+    return IPKGPU_OK;
+}
+
+int ipkgpu_parts_spill(ipkgpu_ctx* ctx, ipkgpu_parts* parts, const char* dir, uint32_t piece, uint64_t* bytes_written)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (!parts || parts->ctx != ctx || !dir) return fail(ctx, IPKGPU_ERR_INVALID, "bad argument");
+    if (parts->d_positions) return fail(ctx, IPKGPU_ERR_INVALID, "positioned parts are not spilled: the on-disk build keeps no positions (as the reference's, db_builder.cpp:469)");
+    if (parts->lead != 0) return fail(ctx, IPKGPU_ERR_INVALID, "key-range parts are not spilled: a key-range pass already bounds the device");
+    if (!parts->d_counts || !parts->d_entries) return fail(ctx, IPKGPU_ERR_INVALID, "these parts' arrays have moved into a database");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t B = parts->n_owners;
+    const uint64_t slots = parts->slots, W = ipkspill::bit_words(slots), n_words = (uint64_t)B * W;
+    if (W > 0xFFFFFFFFull || (n_words + 3) / 4 > 0x7FFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many key slots to spill");
+    RC_TRY(ensure(ctx, ctx->sp_bits, n_words * 8));
+    RC_TRY(ensure(ctx, ctx->sp_pops, n_words * 4));
+    RC_TRY(ensure(ctx, ctx->sp_rank, (n_words + 1) * 8));
+    RC_TRY(ensure(ctx, ctx->goff, ((size_t)B + 1) * 8));
+    uint32_t* d_big = small_at(ctx, SMALL_REC_BIG);
+    HIP_TRY(ctx, hipMemsetAsync(d_big, 0, 4, ctx->stream));
+    const uint32_t grid = (uint32_t)((n_words + 3) / 4);
+    hipLaunchKernelGGL(spill_bits_kernel, dim3(grid), dim3(256), 0, ctx->stream, parts->d_counts, slots, W, n_words,
+                       ctx->sp_bits.as<unsigned long long>(), ctx->sp_pops.as<uint32_t>(), d_big);
+    HIP_TRY(ctx, hipGetLastError());
+    RC_TRY(scan_u32(ctx, ctx->sp_pops.as<uint32_t>(), n_words, ctx->sp_rank.as<uint64_t>()));
+    // every owner's first rank = the number of keys before its row
+    hipLaunchKernelGGL(gather_offsets_kernel, dim3((B + 1 + 255) / 256), dim3(256), 0, ctx->stream, ctx->sp_rank.as<uint64_t>(), (uint32_t)W, B + 1,
+                       ctx->goff.as<uint64_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint64_t> key_base((size_t)B + 1);
+    uint32_t h_big = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(key_base.data(), ctx->goff.p, ((size_t)B + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_big, d_big, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_big) return fail(ctx, IPKGPU_ERR_INVALID, "a key with more than %u entries in one piece: a spill block's counts are 16-bit (pieces of at most %u groups)",
+                           ipkspill::COUNT_MAX, ipkspill::COUNT_MAX);
+    RC_TRY(ensure(ctx, ctx->sp_c16, key_base[B] * 2));
+    hipLaunchKernelGGL(spill_pack_kernel, dim3(grid), dim3(256), 0, ctx->stream, parts->d_counts, slots, W, n_words, ctx->sp_rank.as<uint64_t>(),
+                       ctx->sp_c16.as<uint16_t>());
+    HIP_TRY(ctx, hipGetLastError());
+
+    // the blocks' bytes, chunk by chunk through the two staging buffers: chunk j + 1 is copied off the device while chunk j is written
+    uint64_t largest = 0;
+    for (uint32_t o = 0; o < B; ++o)
+        largest = std::max(largest, ipkspill::file_bytes(slots, key_base[o + 1] - key_base[o], parts->owner_off[o + 1] - parts->owner_off[o]));
+    RC_TRY(spill_stage(ctx, largest));
+    const uint64_t cap = ctx->h_spill_cap;
+    struct Chunk { uint32_t owner = 0; uint64_t bytes = 0; bool first = false, last = false, pending = false; } chunk[2];
+    FILE* fh = nullptr;
+    std::string tmp_path, final_path;
+    uint64_t total = 0;
+    auto abandon = [&]() { if (fh) { fclose(fh); fh = nullptr; } if (!tmp_path.empty()) (void)remove(tmp_path.c_str()); (void)hipStreamSynchronize(ctx->stream); };
+    auto write_chunk = [&](int b) -> int {
+        Chunk& c = chunk[b];
+        if (!c.pending) return IPKGPU_OK;
+        c.pending = false;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_spill[b]));
+        if (c.first) {
+            final_path = spill_block_path(dir, piece, c.owner);
+            tmp_path = final_path + ".tmp";
+            fh = fopen(tmp_path.c_str(), "wb");
+            if (!fh) { const std::string p = tmp_path; tmp_path.clear(); return fail(ctx, IPKGPU_ERR_INVALID, "cannot create %s", p.c_str()); }
+            setvbuf(fh, nullptr, _IONBF, 0);
+        }
+        if (fwrite(ctx->h_spill[b], 1, c.bytes, fh) != c.bytes) return fail(ctx, IPKGPU_ERR_INVALID, "write failed: %s", tmp_path.c_str());
+        total += c.bytes;
+        if (c.last) {
+            const int rc = fclose(fh);
+            fh = nullptr;
+            if (rc != 0) return fail(ctx, IPKGPU_ERR_INVALID, "close failed: %s", tmp_path.c_str());
+            if (rename(tmp_path.c_str(), final_path.c_str()) != 0) return fail(ctx, IPKGPU_ERR_INVALID, "cannot rename %s", tmp_path.c_str());
+            tmp_path.clear();
+        }
+        return IPKGPU_OK;
+    };
+    uint64_t n_chunks = 0;
+    int rc = IPKGPU_OK;
+    for (uint32_t o = 0; o < B && rc == IPKGPU_OK; ++o) {
+        const uint64_t nk = key_base[o + 1] - key_base[o], ne = parts->owner_off[o + 1] - parts->owner_off[o];
+        const ipkspill::Head head = ipkspill::make_head(parts->sigma, parts->k, B, o, piece, slots, nk, ne);
+        const SpillSeg segs[4] = {
+            {0, sizeof head, &head, nullptr},
+            {ipkspill::bits_at(), ipkspill::bits_bytes(slots), nullptr, ctx->sp_bits.as<unsigned long long>() + (uint64_t)o * W},
+            {ipkspill::counts_at(slots), nk * 2, nullptr, ctx->sp_c16.as<uint16_t>() + key_base[o]},
+            {ipkspill::entries_at(slots, nk), ipkspill::entries_bytes(ne), nullptr, parts->d_entries + parts->owner_off[o]}};
+        const uint64_t size = ipkspill::file_bytes(slots, nk, ne);
+        for (uint64_t lo = 0; lo < size && rc == IPKGPU_OK; lo += cap) {
+            const uint64_t hi = std::min(size, lo + cap);
+            const int b = (int)(n_chunks++ & 1);
+            if ((rc = write_chunk(b)) != IPKGPU_OK) break;            // (what this buffer held two chunks ago)
+            char* dst = static_cast<char*>(ctx->h_spill[b]);
+            memset(dst, 0, hi - lo);                                   // (the padding behind the counts)
+            for (const SpillSeg& sg : segs) {
+                const uint64_t a = std::max(lo, sg.at), e = std::min(hi, sg.at + sg.bytes);
+                if (a >= e) continue;
+                if (sg.src) memcpy(dst + (a - lo), static_cast<const char*>(sg.src) + (a - sg.at), e - a);
+                else if (hipMemcpyAsync(dst + (a - lo), static_cast<const char*>(sg.dev) + (a - sg.at), e - a, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+                    rc = fail(ctx, IPKGPU_ERR_HIP, "copy of a spill block off the device failed");
+            }
+            if (rc == IPKGPU_OK && hipEventRecord(ctx->ev_spill[b], ctx->stream) != hipSuccess) rc = fail(ctx, IPKGPU_ERR_HIP, "hipEventRecord failed");
+            chunk[b].owner = o; chunk[b].bytes = hi - lo; chunk[b].first = lo == 0; chunk[b].last = hi == size; chunk[b].pending = rc == IPKGPU_OK;
+        }
+    }
+    if (rc == IPKGPU_OK) rc = write_chunk((int)(n_chunks & 1));       // the older of the two chunks still owed, then the newer
+    if (rc == IPKGPU_OK) rc = write_chunk((int)((n_chunks + 1) & 1));
+    if (rc != IPKGPU_OK) { abandon(); return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes_written) *bytes_written = total;
+    return IPKGPU_OK;
+}
+
+int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t owner, uint32_t n_owners, const char* const* block_paths,
+                       uint32_t n_blocks, ipkgpu_db** out)
+{
+    // (the files are checked first, on the host alone: a bad block is reported, by name, whatever the state of the device)
+    if (out) *out = nullptr;
+    if (!block_paths || n_blocks == 0) return fail(ctx, IPKGPU_ERR_INVALID, "no spill blocks given");
+    if ((sigma != 4 && sigma != 20) || k < 2 || k > ipkgpu_max_k(sigma)) return fail(ctx, IPKGPU_ERR_INVALID, "unsupported sigma/k");
+    if (n_owners == 0 || owner >= n_owners) return fail(ctx, IPKGPU_ERR_INVALID, "bad owner/source counts");
+    const uint64_t T = ipow(sigma, (int)k);
+    const uint64_t slots = (T + n_owners - 1) / n_owners, W = ipkspill::bit_words(slots);
+    std::vector<SpillFile> files;
+    RC_TRY(spill_check_files(ctx, sigma, k, owner, n_owners, block_paths, n_blocks, slots, files));
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (!out) return fail(ctx, IPKGPU_ERR_INVALID, "null out pointer");
+    const uint32_t S = n_blocks;
+    const uint64_t n_words = (uint64_t)S * W;
+    if ((n_words + 3) / 4 > 0x7FFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many key slots in the blocks of one batch");
+    const uint64_t nk_all = files.back().key_base + files.back().head.n_keys, ne_all = files.back().entry_base + files.back().head.n_entries;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ipkgpu_db* db = new (std::nothrow) ipkgpu_db();
+    if (!db) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
+    db->ctx = ctx;
+    struct Guard { ipkgpu_db* r; ~Guard() { if (r) ipkgpu_db_free(r); } } guard{db};
+    uint32_t* d_rows = nullptr; uint2* d_ent = nullptr;
+    struct BGuard { ipkgpu_ctx* c; uint32_t*& a; uint2*& b; ~BGuard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, a); ctx_release(c, b); } } bguard{ctx, d_rows, d_ent};
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&d_rows, (size_t)S * slots * 4));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&d_ent, std::max<uint64_t>(ne_all, 1) * 8));
+    RC_TRY(ensure(ctx, ctx->sp_bits, n_words * 8));
+    RC_TRY(ensure(ctx, ctx->sp_pops, n_words * 4));
+    RC_TRY(ensure(ctx, ctx->sp_rank, (n_words + 1) * 8));
+    RC_TRY(ensure(ctx, ctx->sp_c16, nk_all * 2));
+    uint64_t largest = 0;
+    for (const SpillFile& f : files) largest = std::max(largest, ipkspill::file_bytes(slots, f.head.n_keys, f.head.n_entries));
+    RC_TRY(spill_stage(ctx, largest));
+    const uint64_t cap = ctx->h_spill_cap;
+
+    // the blocks in the order given, chunk by chunk through the staging buffers: a chunk is read while the one before it is uploaded;
+    // on its way the host counts the bits and adds up the counts -- a block whose body disagrees with its head launches nothing
+    uint64_t n_chunks = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const SpillFile& f = files[s];
+        const uint64_t nk = f.head.n_keys, ne = f.head.n_entries;
+        const SpillSeg segs[3] = {
+            {ipkspill::bits_at(), ipkspill::bits_bytes(slots), nullptr, ctx->sp_bits.as<unsigned long long>() + (uint64_t)s * W},
+            {ipkspill::counts_at(slots), nk * 2, nullptr, ctx->sp_c16.as<uint16_t>() + f.key_base},
+            {ipkspill::entries_at(slots, nk), ipkspill::entries_bytes(ne), nullptr, d_ent + f.entry_base}};
+        const uint64_t size = ipkspill::file_bytes(slots, nk, ne);
+        FILE* fh = fopen(f.path.c_str(), "rb");
+        if (!fh) return fail(ctx, IPKGPU_ERR_INVALID, "cannot open spill block %s", f.path.c_str());
+        struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fh};
+        setvbuf(fh, nullptr, _IONBF, 0);
+        uint64_t bits_set = 0, counts_sum = 0;
+        for (uint64_t lo = 0; lo < size; lo += cap) {
+            const uint64_t hi = std::min(size, lo + cap);
+            const int b = (int)(n_chunks++ & 1);
+            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_spill[b]));        // (the uploads out of this buffer two chunks ago; at once on a fresh event)
+            char* src = static_cast<char*>(ctx->h_spill[b]);
+            if (fread(src, 1, hi - lo, fh) != hi - lo) return fail(ctx, IPKGPU_ERR_INVALID, "spill block %s: read failed (truncated?)", f.path.c_str());
+            for (int i = 0; i < 3; ++i) {
+                const SpillSeg& sg = segs[i];
+                const uint64_t a = std::max(lo, sg.at), e = std::min(hi, sg.at + sg.bytes);
+                if (a >= e) continue;
+                if (i == 0) { const uint64_t* w = reinterpret_cast<const uint64_t*>(src + (a - lo)); for (uint64_t j = 0; j < (e - a) / 8; ++j) bits_set += (uint64_t)__builtin_popcountll(w[j]); }
+                if (i == 1) { const uint16_t* c = reinterpret_cast<const uint16_t*>(src + (a - lo)); for (uint64_t j = 0; j < (e - a) / 2; ++j) counts_sum += c[j]; }
+                HIP_TRY(ctx, hipMemcpyAsync(const_cast<char*>(static_cast<const char*>(sg.dev)) + (a - sg.at), src + (a - lo), e - a, hipMemcpyHostToDevice, ctx->stream));
+            }
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_spill[b], ctx->stream));
+        }
+        if (bits_set != nk || counts_sum != ne)
+            return fail(ctx, IPKGPU_ERR_INVALID, "spill block %s: its body disagrees with its head (%llu bits set for %llu keys, counts adding up to %llu for %llu entries)",
+                        f.path.c_str(), (unsigned long long)bits_set, (unsigned long long)nk, (unsigned long long)counts_sum, (unsigned long long)ne);
+    }
+    Stopwatch sw(ctx->stream, &ctx->events);
+    const int t0 = sw.mark();
+    hipLaunchKernelGGL(spill_pops_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, ctx->stream, ctx->sp_bits.as<unsigned long long>(), n_words,
+                       ctx->sp_pops.as<uint32_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    RC_TRY(scan_u32(ctx, ctx->sp_pops.as<uint32_t>(), n_words, ctx->sp_rank.as<uint64_t>()));
+    hipLaunchKernelGGL(spill_unpack_kernel, dim3((uint32_t)((n_words + 3) / 4)), dim3(256), 0, ctx->stream, ctx->sp_bits.as<unsigned long long>(),
+                       ctx->sp_rank.as<uint64_t>(), ctx->sp_c16.as<uint16_t>(), nk_all, slots, W, n_words, d_rows);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<const uint32_t*> crow(S);
+    std::vector<const uint2*> srow(S);
+    for (uint32_t s = 0; s < S; ++s) { crow[s] = d_rows + (size_t)s * slots; srow[s] = d_ent + files[s].entry_base; }
+    RC_TRY(ensure(ctx, ctx->counts, slots * 4));
+    RC_TRY(merge_sources(ctx, sigma, k, owner, n_owners, S, slots, crow, srow, ctx->counts.as<uint32_t>(), &db->d_entries, &db->n_entries, db));
+    const int t1 = sw.mark();
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    db->t_merge = sw.ms(t0, t1);
+    guard.r = nullptr;
+    *out = db;
     return IPKGPU_OK;
 }
 

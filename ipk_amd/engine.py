@@ -404,6 +404,15 @@ def _bind_keymajor(L):
         getattr(L, n).argtypes = [C.c_void_p]
     L.ipkgpu_db_filter_time_ms.restype = C.c_double
     L.ipkgpu_db_filter_time_ms.argtypes = [C.c_void_p]
+    L.ipkgpu_parts_spill.restype = C.c_int
+    L.ipkgpu_parts_spill.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, u64p]
+    L.ipkgpu_spill_merge.restype = C.c_int
+    L.ipkgpu_spill_merge.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                     C.POINTER(C.c_void_p)]
+    L.ipkgpu_mem_stats.restype = C.c_int
+    L.ipkgpu_mem_stats.argtypes = [C.c_void_p, u64p, u64p, C.c_int]
+    L.ipkgpu_get_option.restype = C.c_int
+    L.ipkgpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
     L._km_bound = True
 
 
@@ -424,6 +433,7 @@ ABI_SYMBOLS += [
     "ipkgpu_score_groups_keymajor_positions_device", "ipkgpu_parts_positions_device", "ipkgpu_db_positions",
     "ipkgpu_db_positions_device",
     "ipkgpu_score_groups_keymajor_positions_owners_device", "ipkgpu_merge_parts_positions_ptrs",
+    "ipkgpu_parts_spill", "ipkgpu_spill_merge", "ipkgpu_mem_stats", "ipkgpu_get_option",
 ]
 
 
@@ -787,3 +797,52 @@ def _score_groups_keymajor_positions_owners(self, logp, mat_group, k, log_eps, n
 
 Engine.score_groups_keymajor_positions_owners = _score_groups_keymajor_positions_owners
 Engine.merge_parts = _merge_parts
+
+
+def _parts_spill(self, parts, directory, piece):
+    """Packs and writes every owner block of `parts` as directory/p<piece>_b<owner>.blk (include/ipkgpu.h, ipkgpu_parts_spill);
+    returns the bytes written."""
+    _bind_keymajor(self._lib)
+    n = C.c_uint64(0)
+    rc = self._lib.ipkgpu_parts_spill(self._h, parts._h, os.fsencode(directory), int(piece), C.byref(n))
+    if rc != 0:
+        raise self._err(rc)
+    return int(n.value)
+
+
+def _spill_merge(self, sigma, k, owner, n_owners, block_paths):
+    """One batch's database out of its spill blocks, read in the order given = piece order (ipkgpu_spill_merge)."""
+    _bind_keymajor(self._lib)
+    n = len(block_paths)
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in block_paths])
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_spill_merge(self._h, sigma, k, owner, n_owners, arr, n, C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return self._adopt(Db(self._lib, out))
+
+
+def _mem_stats(self, reset_peak=False):
+    """(held, held_peak): bytes of device memory the context holds from hipMalloc, and their high-water mark (ipkgpu_mem_stats)."""
+    _bind_keymajor(self._lib)
+    held, peak = C.c_uint64(0), C.c_uint64(0)
+    rc = self._lib.ipkgpu_mem_stats(self._h, C.byref(held), C.byref(peak), 1 if reset_peak else 0)
+    if rc != 0:
+        raise self._err(rc)
+    return int(held.value), int(peak.value)
+
+
+def _get_option(self, name):
+    """"workspace_bytes", "device_budget_bytes" or "last_refused_bytes" (ipkgpu_get_option)."""
+    _bind_keymajor(self._lib)
+    v = C.c_int64(0)
+    rc = self._lib.ipkgpu_get_option(self._h, name.encode(), C.byref(v))
+    if rc != 0:
+        raise IpkGpuError(rc, f"no readable option '{name}'")
+    return int(v.value)
+
+
+Engine.get_option = _get_option
+Engine.parts_spill = _parts_spill
+Engine.spill_merge = _spill_merge
+Engine.mem_stats = _mem_stats
