@@ -27,10 +27,14 @@
  * DNA k = 15, 16 are built in key-range passes instead (ipkgpu_score_groups_keyrange_device: the k-mers of one class of
  * leading symbols per call, one owner; each pass' shard written as a file of its own, the files merged by
  * ipkgpu_db_merge_files) -- not on several ranks (owners inside a key range would need a slot mapping of their own), not
- * through the per-branch result or the positions path, not for amino acids k = 7 (35-bit keys).  At DNA k >= 13 also
- * a call in which one window's half list (its 6- to 8-symbol prefixes or suffixes above their threshold) exceeds 6144
- * entries, by every scoring entry point, ipkgpu_score_groups_positions included: near-uniform columns, which real
- * posteriors do not have.  The reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group files
+ * through the per-branch result or the positions path, not for amino acids k = 7 (35-bit keys).
+ * DNA k >= 13: the kernels that score a window with long half lists (its 6- to 8-symbol prefixes or suffixes above their
+ * threshold) keep a list of at most 6144 entries in LDS.  By default a call in which one window's half list is longer fails
+ * (every scoring entry point, ipkgpu_score_groups_positions included); near-flat columns get there, and among the hundreds
+ * of thousands of windows of an alignment of ordinary length at k = 15, 16 a few do.  With the option "slice_long_lists" = 1
+ * such a window is scored one class of the list's leading symbols at a time (a 7-symbol half in 4 slices, an 8-symbol half
+ * in 16, each at most 4^6 entries), the same k-mers and score bits as the reference's, and no call fails for its lists.
+ * The reference's on-disk mode (db_builder.cpp:673-681, branch_group.cpp:109-185: per-group files
  * merged later) is ipkgpu_parts_spill / ipkgpu_spill_merge below: one GPU, no positions, no key-range passes.
  */
 #ifndef IPKGPU_H
@@ -105,6 +109,10 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * per key block / per run of key blocks whatever the group count), "debug_pool_chunks", "debug_pool_limit_bytes",
  * "debug_wg_chunks2", "debug_rounds", "debug_kmc_pass" (groups per pass of the compressed key-major writer),
  * "debug_prefix_mats" (matrices per workgroup of the prefix-sum kernel: 1, 2, 4, 8; 0 = by the matrix count) (diagnostics and tests only);
+ * "slice_long_lists" (0 / 1, default 0; DNA k >= 13 only: 1 = a window whose half list exceeds the 6144 entries the big-list
+ * kernels keep in LDS is scored in slices instead of failing the call -- see "Not supported" above; applies to every scoring entry
+ * point: per-branch result, key-major with and without owners or positions, key-range passes, ipkgpu_score_groups_positions, the
+ * pieces of the on-disk build; results of calls without such a window do not change);
  * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
  * Every variant yields identical results.  Returns IPKGPU_ERR_INVALID for unknown names.
@@ -345,7 +353,8 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
  * first drops the cached blocks and, if it still would, fails with IPKGPU_ERR_NOMEM; work sized by free device memory sees at most what
  * the budget leaves.  The context stays usable after such a failure.  Device memory of the caller (the matrices) is not counted. */
 int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak);
-/* Reads back "workspace_bytes" or "device_budget_bytes" (a caller that sets them for a while restores them), or "last_refused_bytes":
+/* Reads back "workspace_bytes", "device_budget_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
+ * "debug_sliced_windows" (the windows this context has scored in slices so far), or "last_refused_bytes":
  * the bytes held plus the size of the last allocation the device or the budget refused -- what the failed step needed at least.
  * IPKGPU_ERR_INVALID for other names. */
 int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value);

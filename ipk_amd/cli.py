@@ -185,6 +185,9 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     t_load = time.time() - t0
     log_eps = ipk_amd.log_threshold(omega, sigma, k)
     eng = ipk_amd.Engine(device)
+    # the reference's command computes every window (its lists live in host memory): a DNA k >= 13 window whose half list exceeds
+    # the big-list kernels' capacity is scored slice by slice instead of ending the build (no effect at other k)
+    eng.set_option("slice_long_lists", 1)
     if use_passes:
         n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
         kr = keyrange.build_db_file(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, output, workdir,

@@ -230,11 +230,12 @@ __device__ __forceinline__ uint32_t join_to_list(const uint2* L, uint32_t nL, co
 }
 
 // Builds S(J, H, eps) of the window into out[0 .. CAPH); children/scratch follow at out + CAPH.
-// LN > 0 (key-range calls): only the members whose symbols at window positions [0, LN) spell c.lead_c, coded relative to
-// that class (code - lead_c * sigma^(K - LN) once joined up to the half list).  The restriction is applied where those
-// symbols enter, in the direct leaves; every bound (eps) depends only on the column maxima, so the members kept are exactly
-// the unrestricted ones of that class, with the same scores.
-template <int SIGMA, int J, int H, int CAP, int LN = 0>
+// LN > 0: only the members whose symbols at window positions [P0, P0 + LN) spell c.lead_c, coded relative to that class
+// (code - lead_c * sigma^(H - LN) for the half list that starts at P0).  P0 = 0 restricts the left half (key-range calls, and the
+// slices of a left half that does not fit the big-list kernels' capped lists), P0 = K / 2 the right half (its slices).  The
+// restriction is applied where those symbols enter, in the direct leaves; every bound (eps) depends only on the column maxima,
+// so the members kept are exactly the unrestricted ones of that class, with the same scores.
+template <int SIGMA, int J, int H, int CAP, int LN = 0, int P0 = 0>
 struct Node {
     using G = Geo<SIGMA, H, CAP>;
     static __device__ __forceinline__ uint32_t build(const WinCtx& c, float eps, uint2* out)
@@ -245,10 +246,12 @@ struct Node {
             bool pass = false;
             uint32_t code = lane;
             if (lane < G::FULL) pass = Direct<SIGMA, J, H>::eval(c, eps, lane, s);
-            if constexpr (LN > J) {
-                constexpr int D = LN - J < H ? LN - J : H;           // class symbols inside this leaf (its leading D)
+            if constexpr (LN > 0 && P0 + LN > J && J + H > P0) {
+                static_assert(J >= P0, "the class symbols start where a leaf starts");
+                constexpr int E = P0 + LN - J;                       // class symbols from this leaf's start on
+                constexpr int D = E < H ? E : H;                     // class symbols inside this leaf (its leading D)
                 constexpr uint32_t LOW = ipow(SIGMA, H - D);
-                const uint32_t v = (c.lead_c / ipow(SIGMA, LN - J - D)) % ipow(SIGMA, D);
+                const uint32_t v = (c.lead_c / ipow(SIGMA, E - D)) % ipow(SIGMA, D);
                 pass = pass && lane / LOW == v;
                 code = lane - v * LOW;
             }
@@ -262,9 +265,9 @@ struct Node {
             const float eps_r = eps - (c.best[c.w + J + HL] - c.best[c.w + J]);       // :55
             uint2* lp = out + G::CAPH;
             uint2* rp = lp + GL::CAPH;
-            const uint32_t nl = Node<SIGMA, J, HL, CAP, LN>::build(c, eps_l, lp);
+            const uint32_t nl = Node<SIGMA, J, HL, CAP, LN, P0>::build(c, eps_l, lp);
             if (nl == LIST_OVERFLOW || nl == 0) return nl;
-            const uint32_t nr = Node<SIGMA, J + HL, HR, CAP, LN>::build(c, eps_r, rp);
+            const uint32_t nr = Node<SIGMA, J + HL, HR, CAP, LN, P0>::build(c, eps_r, rp);
             if (nr == LIST_OVERFLOW || nr == 0) return nr;
             wave_lds_sync();
             const uint32_t n = join_to_list(lp, nl, rp, nr, eps, ipow(SIGMA, HR), out, G::CAPH);

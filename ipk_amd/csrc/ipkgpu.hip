@@ -107,6 +107,8 @@ struct ipkgpu_ctx {
     int64_t opt_variant = 0;
     int64_t opt_flags = 0;
     int64_t opt_kmc_pass = 0;            // groups per pass of the compressed key-major writer (0: IPK_KMC_PASS)
+    int64_t opt_slice = 0;               // "slice_long_lists": DNA k >= 13 windows beyond the capped big-list capacity are scored in slices
+    uint64_t sliced_windows = 0;         // such windows so far (get_option "debug_sliced_windows")
     int64_t opt_prefix_mats = 0;         // matrices per workgroup of prefix_max_kernel (0: by the matrix count; 1, 2, 4, 8: tests)
     int64_t opt_wg_chunks2 = 0;       // tuning knob: overrides IPK_WG_CHUNKS2 (0 = built-in), opt_rounds: IPK_ROUNDS
     int64_t opt_rounds = 0;
@@ -499,6 +501,11 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
         for (DevBuf* b : all_workspaces(ctx)) if (b->p) { (void)dev_free(ctx, b->p, b->cap); b->p = nullptr; b->cap = 0; }
         drop_cache(ctx);
         ctx->mask_valid = false; ctx->pend.active = false; ctx->pend.sw.reset();
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "slice_long_lists")) {
+        if (value != 0 && value != 1) return fail(ctx, IPKGPU_ERR_INVALID, "slice_long_lists is 0 or 1");
+        ctx->opt_slice = value;
         return IPKGPU_OK;
     }
     if (!strcmp(name, "variant")) { ctx->opt_variant = value; return IPKGPU_OK; }
@@ -1120,6 +1127,7 @@ int score_batch_xp(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uint3
     sp.eps = pl.eps;
     sp.pool = nullptr; sp.pool_cap = 0; sp.pool_next = nullptr; sp.desc = nullptr; sp.pool_ovf = nullptr; sp.pre_chunks = 0;
     sp.emitted = p.emitted; sp.ovf_queue = p.ovf_queue; sp.ovf_count = p.ovf_count; sp.mat_slot = p.mat_slot; sp.big_ovf = p.big_ovf;
+    sp.slice_lists = p.slice_lists;
     sp.flags = (uint32_t)(ctx->opt_flags) & 4u;      // (bit 2: list building only -- timing experiments)
     xp.cnt = ctx->gbcnt.as<uint32_t>();
     xp.off = ctx->gboff.as<uint64_t>();
@@ -1248,21 +1256,27 @@ int stream_batch_check(ipkgpu_ctx* ctx)
 
 // Capped big-list capacity (DNA k >= 13, kernels_score.hpp big_capf): a window whose half list exceeds BIG_CAP_ENTRIES raises the
 // flag word SMALL_BIG_OVF.  arm_capped points p.big_ovf at it and clears it (null where nothing is capped); check_capped, after
-// the batch's scoring kernels, turns a raised flag into the call's error.
+// the batch's scoring kernels, turns a raised flag into the call's error.  With the option "slice_long_lists" such a window is
+// scored in slices instead (kernels_score.hpp SlicedHalves) and counted in SMALL_SLICED, the word before the flag; the flag can
+// then only mean a bug, and is checked all the same.
 int arm_capped(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, ScoreParams& p)
 {
+    static_assert(SMALL_SLICED + 4 == SMALL_BIG_OVF, "the count and the flag are cleared and read together");
     const bool capped_lists = sigma == 4 && k >= 13;
     p.big_ovf = capped_lists ? small_at(ctx, SMALL_BIG_OVF) : nullptr;
-    if (capped_lists) HIP_TRY(ctx, hipMemsetAsync(p.big_ovf, 0, 4, ctx->stream));
+    p.slice_lists = capped_lists && ctx->opt_slice ? 1u : 0u;
+    if (capped_lists) HIP_TRY(ctx, hipMemsetAsync(p.big_ovf - 1, 0, 8, ctx->stream));      // the count and the flag
     return IPKGPU_OK;
 }
 
 int check_capped(ipkgpu_ctx* ctx, uint32_t k, const ScoreParams& p)
 {
     if (!p.big_ovf) return IPKGPU_OK;
-    uint32_t hit = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&hit, p.big_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    uint32_t word[2] = {0, 0};                               // SMALL_SLICED, SMALL_BIG_OVF
+    HIP_TRY(ctx, hipMemcpyAsync(word, p.big_ovf - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sliced_windows += word[0];
+    const uint32_t hit = word[1];
     if (hit) return fail(ctx, IPKGPU_ERR_INVALID, "a window's half list exceeds %d entries: beyond the capacity of this engine at k = %u "
                                                   "(the lists of k >= 13 are capped; lower omega's reach or k)", BIG_CAP_ENTRIES, k);
     return IPKGPU_OK;
@@ -3069,6 +3083,8 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "workspace_bytes")) { *value = ctx->workspace_bytes; return IPKGPU_OK; }
     if (!strcmp(name, "device_budget_bytes")) { *value = ctx->budget; return IPKGPU_OK; }
     if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
+    if (!strcmp(name, "slice_long_lists")) { *value = ctx->opt_slice; return IPKGPU_OK; }
+    if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
     return IPKGPU_ERR_INVALID;
 }
 

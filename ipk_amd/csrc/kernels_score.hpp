@@ -114,6 +114,8 @@ struct ScoreParams {
     const uint32_t* mat_slot;     // [n_mats] table slot of each matrix within this batch
     uint32_t n_batch_mats, sites, nwin, tiles_per_mat;
     float eps;
+    uint32_t slice_lists = 0;     // capped lists (big_capf, DNA k >= 13): 1 = a window whose half list exceeds the capacity is scored slice by slice
+                                  // (SlicedHalves) and counted in big_ovf[-1] instead of raising *big_ovf  (sits in the padding behind eps: no offset moves)
     void* table;                  // [slots][table_size] u32 score codes; u64 (code << 32 | ~sequence) when positions are kept
     uint64_t table_size;
     const uint32_t* mat_rank;     // [n_mats] rank of each matrix inside its group (positions variant only)
@@ -123,7 +125,8 @@ struct ScoreParams {
     uint32_t flags;               // bit 0 (diagnostic builds of bench only): skip the table update
     uint32_t* mask;               // [slots][mask_words] occupancy bits of the tables (bit x % 32 of word x / 32), or null:
     uint64_t mask_words;          //   written by the LDS reduce passes, kept current by the big-list kernel
-    uint32_t* big_ovf = nullptr;  // set when a window's half list exceeds the big-list kernels' capped capacity (big_capf, DNA k >= 13)
+    uint32_t* big_ovf = nullptr;  // set when a window's half list exceeds the big-list kernels' capped capacity (big_capf, DNA k >= 13);
+                                  // big_ovf[-1] counts the windows scored in slices (SMALL_SLICED)
 };
 
 // ipk::put (branch_group.cpp:88-101): keep the larger score; the first one wins ties.
@@ -269,6 +272,90 @@ template <int SIGMA, int K> constexpr int big_capf()
     return (size_t)wave_scratch_entries<SIGMA, K, 1 << 30>() * 8 <= (size_t)136 * 1024 ? (1 << 30) : BIG_CAP_ENTRIES;
 }
 
+// Sliced big-list windows (capped lists only: big_capf == BIG_CAP_ENTRIES, DNA k >= 13; ScoreParams::slice_lists).  A half list
+// that does not fit the cap is built and joined one class of its leading symbols at a time (Node's restriction): a half of H symbols
+// by its leading H - 6, so a slice has at most 4^6 = 4096 entries and cannot overflow -- 4 classes for a 7-symbol half, 16 for an
+// 8-symbol one.  The window is then the union over (class of L) x (class of R); a half that fits whole is built whole.  The left
+// half of a key-range call (LN leading symbols fixed by the pass) has at most 4^6 members and is never sliced.
+// Wave 0 calls step() once per (cl, cr) in the order cl-major, and publishes the counts; the slices live where the capped lists do.
+template <int SIGMA, int K, int CAP, int LN>
+struct SlicedHalves {
+    static constexpr int HL = K / 2, HR = K - K / 2;
+    static constexpr int FREE = 6;                                          // symbols a slice leaves free
+    static constexpr int NLT = HL - FREE > LN ? HL - FREE : LN;            // restricted leading symbols of a sliced L: the pass' and the slice's
+    static constexpr int SL = NLT - LN, SR = HR > FREE ? HR - FREE : 0;    // symbols that name a slice
+    static constexpr uint32_t NCL = ipow(SIGMA, SL), NCR = ipow(SIGMA, SR);
+    static constexpr uint32_t BASE_L = ipow(SIGMA, HL - NLT), BASE_R = ipow(SIGMA, HR - SR);   // what a class adds to its members' codes
+    using GL = Geo<SIGMA, HL, CAP>;
+    static constexpr uint32_t LAST_R = 1u, LAST_L = 2u, SLICED = 4u;
+
+    uint32_t nl = 0, nr = 0;            // the lists in LDS now (wave 0's registers)
+    bool l_over = false, r_over = false, dead = false;
+
+    // slice codes come out relative to the class: the class base goes back on in LDS, so the join sees full (pass-relative) codes
+    static __device__ __forceinline__ void add_base(uint2* list, uint32_t n, uint32_t base)
+    {
+        wave_lds_sync();
+        if (base) for (uint32_t i = lane_id(); i < n; i += 64) list[i].x += base;
+        wave_lds_sync();
+    }
+
+    // The lists of (cl, cr) into scratch; returns LAST_R when the classes of R are done for this class of L, LAST_L likewise for L,
+    // SLICED (first step only) when the window takes slices.  Without slice_on an overflow raises *big_ovf and empties the window.
+    __device__ __forceinline__ uint32_t step(const WinCtx& c, float eps, uint2* scratch, uint32_t cl, uint32_t cr, bool slice_on,
+                                             uint32_t* big_ovf)
+    {
+        static_assert(SIGMA == 4 && CAP == BIG_CAP_ENTRIES, "the capped lists of DNA k >= 13");
+        static_assert(BASE_L <= (uint32_t)CAP && BASE_R <= (uint32_t)CAP, "a slice cannot overflow");
+        const float eps_l = eps - (c.best[c.w + K] - c.best[c.w + HL]);    // pk_compute.cpp:54
+        const float eps_r = eps - (c.best[c.w + HL] - c.best[c.w]);        // :55
+        uint2* lp = scratch;
+        uint2* rp = scratch + GL::CAPH;
+        const bool first = cl == 0 && cr == 0;
+        if (cr == 0) {
+            if (first) {
+                nl = Node<SIGMA, 0, HL, CAP, LN>::build(c, eps_l, lp);
+                l_over = nl == LIST_OVERFLOW; r_over = false;                  // (a new window: nothing is left of the last one's state)
+                dead = nl == 0 || (l_over && (!slice_on || SL == 0));
+            }
+            if constexpr (SL > 0) {
+                if (l_over && !dead) {
+                    WinCtx cs = c;
+                    cs.lead_c = c.lead_c * NCL + cl;
+                    nl = Node<SIGMA, 0, HL, CAP, NLT>::build(cs, eps_l, lp);
+                    add_base(lp, nl, cl * BASE_L);
+                }
+            }
+            // R's region holds L's children whenever L has been built: the whole R again, unless it is known not to fit
+            if (!dead && (first || (l_over && !r_over && nl != 0))) {
+                nr = Node<SIGMA, HL, HR, CAP>::build(c, eps_r, rp);
+                if (first) {
+                    r_over = nr == LIST_OVERFLOW;
+                    dead = nr == 0 || (r_over && (!slice_on || SR == 0));
+                }
+            }
+        }
+        if constexpr (SR > 0) {
+            if (r_over && !dead && nl != 0) {
+                WinCtx cs = c;
+                cs.lead_c = cr;
+                nr = Node<SIGMA, HL, HR, CAP, SR, HL>::build(cs, eps_r, rp);
+                add_base(rp, nr, cr * BASE_R);
+            }
+        }
+        if (dead) {
+            nl = 0; nr = 0;
+            if (first && (l_over || r_over) && lane_id() == 0 && big_ovf) atomicOr(big_ovf, 1u);   // capped lists: the call fails
+        }
+        wave_lds_sync();
+        uint32_t flags = 0;
+        if (dead || !r_over || nl == 0 || cr + 1 == NCR) flags |= LAST_R;
+        if (dead || !l_over || cl + 1 == NCL) flags |= LAST_L;
+        if (first && !dead && (l_over || r_over)) flags |= SLICED;
+        return flags;
+    }
+};
+
 template <int SIGMA, int K, bool POS = false>
 __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_kernel(ScoreParams p)
 {
@@ -283,7 +370,16 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_kernel(ScoreParams
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     unsigned long long emitted = 0;                     // per-wave count of scored phylo-k-mers (can pass 2^32 on flat data)
     constexpr uint32_t mulR = ipow(SIGMA, K - K / 2);
-    for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
+    // Capped lists (CAPPED; SlicedHalves): a window whose half list does not fit takes one trip of this loop per (class of L, class of R)
+    // -- `more` holds q back -- with wave 0's state carried from trip to trip; every trip stages the columns and passes the barriers
+    // like a window of its own, and what ends the slices are the flags wave 0 leaves above the count in sh_n[0], read after the
+    // barrier: all waves take the same trips.  Elsewhere `more` is never set and this is the loop it always was.
+    using SH = SlicedHalves<SIGMA, K, CAPF, 0>;
+    constexpr bool CAPPED = CAPF == BIG_CAP_ENTRIES;
+    [[maybe_unused]] SH sh;
+    [[maybe_unused]] uint32_t cl = 0, cr = 0;
+    [[maybe_unused]] bool more = false;
+    for (uint32_t q = blockIdx.x; q < n; q += CAPPED && more ? 0u : gridDim.x) {
         const unsigned long long e = p.ovf_queue[q];
         const uint32_t mat = (uint32_t)(e >> 32), start = (uint32_t)e;
         __syncthreads();                                                       // previous window's lists consumed
@@ -299,13 +395,27 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_kernel(ScoreParams
         const uint2 *L = scratch, *R = scratch + Geo<SIGMA, K / 2, CAPF>::CAPH;
         if (wave == 0) {
             WinCtx c{cols, best, 0};
-            uint32_t nL = 0, nR = 0;
-            const bool fits = build_halves<SIGMA, K, CAPF>(c, p.eps, scratch, L, nL, R, nR);      // (cannot overflow at full capacity)
-            if (!fits) { nL = 0; nR = 0; if (lane == 0 && p.big_ovf) atomicOr(p.big_ovf, 1u); }   // capped lists (big_capf): the call fails
-            if (lane == 0) { sh_n[0] = nL; sh_n[1] = nR; }
+            if constexpr (!CAPPED) {
+                uint32_t nL = 0, nR = 0;
+                const bool fits = build_halves<SIGMA, K, CAPF>(c, p.eps, scratch, L, nL, R, nR);      // (cannot overflow at full capacity)
+                if (!fits) { nL = 0; nR = 0; if (lane == 0 && p.big_ovf) atomicOr(p.big_ovf, 1u); }
+                if (lane == 0) { sh_n[0] = nL; sh_n[1] = nR; }
+            } else {
+                const uint32_t f = sh.step(c, p.eps, scratch, cl, cr, p.slice_lists != 0, p.big_ovf);
+                if (lane == 0) {
+                    sh_n[0] = sh.nl | (f << 16); sh_n[1] = sh.nr;                  // (a capped list: 13 bits)
+                    if ((f & SH::SLICED) && p.big_ovf) atomicAdd(p.big_ovf - 1, 1u);               // (SMALL_SLICED: the word before the flag)
+                }
+            }
         }
         __syncthreads();
-        const uint32_t nL = sh_n[0], nR = sh_n[1];
+        const uint32_t nL = CAPPED ? sh_n[0] & 0xFFFFu : sh_n[0], nR = sh_n[1];
+        if constexpr (CAPPED) {                                                   // the next trip's slice, or the next window
+            const uint32_t last = sh_n[0] >> 16;
+            cr = (last & SH::LAST_R) ? 0u : cr + 1;
+            if (last & SH::LAST_R) cl = (last & SH::LAST_L) ? 0u : cl + 1;
+            more = (cl | cr) != 0;
+        }
         if (nL == 0 || nR == 0) continue;
         uint32_t cnt = 0;
         // A block of 64 entries of R stays in registers while the rows of L (dealt round-robin to the waves) pass by, OVF_ROWS rows per
@@ -394,6 +504,7 @@ struct StreamParams {
     const uint32_t* gm_list;       // matrix indices
     uint32_t sites, nwin, tiles_per_mat, S;   // S = segments (workgroups) per group
     float eps;
+    uint32_t slice_lists = 0;      // capped lists: as ScoreParams::slice_lists (in the padding behind eps: no offset moves)
     uint2* pool;                   // [pool_cap][chunk_pairs<TBL>()] pairs (dense code, score bits)
     uint32_t pool_cap;
     uint32_t* pool_next;           // next free chunk
@@ -849,6 +960,7 @@ constexpr uint32_t SMALL_EMITTED = 0;        // u64 scored phylo-k-mers of the b
 constexpr uint32_t SMALL_OVF_COUNT = 16;     // u32 big-list queue length
 constexpr uint32_t SMALL_POOL_NEXT = 32;     // u32 chunk ids drawn from the pair pool
 constexpr uint32_t SMALL_POOL_OVF = 36;      // u32 the pair pool ran out
+constexpr uint32_t SMALL_SLICED = 40;        // u32 windows scored in slices (DNA k >= 13 with "slice_long_lists")
 constexpr uint32_t SMALL_BIG_OVF = 44;       // u32 a half list exceeded the capped big-list capacity (DNA k >= 13)
 constexpr uint32_t SMALL_OVF_EMITTED = 48;   // u64 the pooled big-list kernel's own count (discarded with the quad kernel)
 constexpr uint32_t SMALL_XP_TOO_BIG = 56;    // u32 a group's exact partition reached 2^32 pairs
@@ -1521,7 +1633,16 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
     const uint32_t n = *p.ovf_count;
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     unsigned long long emitted = 0;
-    for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
+    // Capped lists (CAPPED; SlicedHalves): a window whose half list does not fit takes one trip of this loop per (class of L, class of R)
+    // -- `more` holds q back -- with wave 0's state carried from trip to trip; every trip stages the columns and passes the barriers
+    // like a window of its own, and what ends the slices are the flags wave 0 leaves above the count in sh_n[0], read after the
+    // barrier: all waves take the same trips.  Elsewhere `more` is never set and this is the loop it always was.
+    using SH = SlicedHalves<SIGMA, K, CAPF, LN>;
+    constexpr bool CAPPED = CAPF == BIG_CAP_ENTRIES;
+    [[maybe_unused]] SH sh;
+    [[maybe_unused]] uint32_t cl = 0, cr = 0;
+    [[maybe_unused]] bool more = false;
+    for (uint32_t q = blockIdx.x; q < n; q += CAPPED && more ? 0u : gridDim.x) {
         const unsigned long long e = p.ovf_queue[q];
         const uint32_t mat = (uint32_t)(e >> 32), start = (uint32_t)e;
         const uint32_t g = p.mat_slot[mat];
@@ -1536,13 +1657,27 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_xp_kernel(XpParams
         const uint2 *L = scratch, *R = scratch + Geo<SIGMA, K / 2, CAPF>::CAPH;
         if (wave == 0) {
             WinCtx c{cols, best, 0, xp.lead_c};
-            uint32_t nL = 0, nR = 0;
-            const bool fits = build_halves<SIGMA, K, CAPF, LN>(c, p.eps, scratch, L, nL, R, nR);  // (cannot overflow at full capacity)
-            if (!fits) { nL = 0; nR = 0; if (lane == 0 && p.big_ovf) atomicOr(p.big_ovf, 1u); }   // capped lists (big_capf): the call fails
-            if (lane == 0) { sh_n[0] = nL; sh_n[1] = nR; }
+            if constexpr (!CAPPED) {
+                uint32_t nL = 0, nR = 0;
+                const bool fits = build_halves<SIGMA, K, CAPF, LN>(c, p.eps, scratch, L, nL, R, nR);  // (cannot overflow at full capacity)
+                if (!fits) { nL = 0; nR = 0; if (lane == 0 && p.big_ovf) atomicOr(p.big_ovf, 1u); }
+                if (lane == 0) { sh_n[0] = nL; sh_n[1] = nR; }
+            } else {
+                const uint32_t f = sh.step(c, p.eps, scratch, cl, cr, p.slice_lists != 0, p.big_ovf);
+                if (lane == 0) {
+                    sh_n[0] = sh.nl | (f << 16); sh_n[1] = sh.nr;                  // (a capped list: 13 bits)
+                    if (!WRITE && (f & SH::SLICED) && p.big_ovf) atomicAdd(p.big_ovf - 1, 1u);     // (SMALL_SLICED: the word before the flag)
+                }
+            }
         }
         __syncthreads();
-        const uint32_t nL = sh_n[0], nR_all = sh_n[1];
+        const uint32_t nL = CAPPED ? sh_n[0] & 0xFFFFu : sh_n[0], nR_all = sh_n[1];
+        if constexpr (CAPPED) {                                                   // the next trip's slice, or the next window
+            const uint32_t last = sh_n[0] >> 16;
+            cr = (last & SH::LAST_R) ? 0u : cr + 1;
+            if (last & SH::LAST_R) cl = (last & SH::LAST_L) ? 0u : cl + 1;
+            more = (cl | cr) != 0;
+        }
         if (nL == 0 || nR_all == 0) continue;
         uint32_t n0 = nR_all;                      // NSUB > 1: R's entries in a row's first bucket (a prefix: ascending codes)
         if constexpr (NSUB > 1) {

@@ -227,6 +227,8 @@ class Engine:
         return self._lib.ipkgpu_last_main_kernel(self._h).decode()
 
     def set_option(self, name, value):
+        """ipkgpu_set_option; "slice_long_lists" = 1: DNA k >= 13 windows whose half lists exceed the big-list kernels' capacity are scored
+        in slices instead of failing the call (default 0)."""
         rc = self._lib.ipkgpu_set_option(self._h, name.encode(), int(value))
         if rc != 0:
             raise self._err(rc)
@@ -833,7 +835,8 @@ def _mem_stats(self, reset_peak=False):
 
 
 def _get_option(self, name):
-    """"workspace_bytes", "device_budget_bytes" or "last_refused_bytes" (ipkgpu_get_option)."""
+    """"workspace_bytes", "device_budget_bytes", "last_refused_bytes", "slice_long_lists" or "debug_sliced_windows" (the windows
+    scored in slices by this engine so far) (ipkgpu_get_option)."""
     _bind_keymajor(self._lib)
     v = C.c_int64(0)
     rc = self._lib.ipkgpu_get_option(self._h, name.encode(), C.byref(v))

@@ -1,5 +1,6 @@
 """DNA k = 13, 14 at a cfg3-like shape (the share of one of 8 ranks: 125 groups x 2 matrices x 10 000 sites, alpha 0.05): time per pass of the
-key-major build, keys and entries; k = 12 beside it.  Usage: python tools/k13_probe.py [groups] [sites]"""
+key-major build, keys and entries; k = 12 beside it.  slice = 1 sets the engine option "slice_long_lists" (this input has no window
+beyond the big-list cap: the option's cost where nothing is sliced).  Usage: python tools/k13_probe.py [groups] [sites] [ks] [slice]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,6 +16,8 @@ dev = torch.from_numpy(mats).cuda()
 eng = ipk_amd.Engine(0)
 if os.environ.get("IPKGPU_DEBUG_FLAGS"):
     eng.set_option("debug_flags", int(os.environ["IPKGPU_DEBUG_FLAGS"]))
+if len(sys.argv) > 4 and int(sys.argv[4]):
+    eng.set_option("slice_long_lists", 1)
 from ipk_amd import engine as E
 ks = [int(x) for x in sys.argv[3].split(",")] if len(sys.argv) > 3 else [12, 13, 14]
 for k in ks:
@@ -46,4 +49,6 @@ for k in ks:
             print(f"  filter values of 600 keys over {nk} keys agree with the oracle (worst relative difference {worst:.1e}), {db.filter_time_ms():.2f} ms", flush=True)
         db.free(); parts.free()
     st = eng.last_stats() if hasattr(eng, "last_stats") else None
+    if len(sys.argv) > 4 and int(sys.argv[4]):
+        print(f"  windows scored in slices so far: {eng.get_option('debug_sliced_windows')}")
     print(f"k={k} groups={groups} sites={sites}: {min(ts[1:]):.2f} ms per pass (first {ts[0]:.1f}), keys {nk}, entries {ne}", flush=True)

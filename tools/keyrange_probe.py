@@ -1,7 +1,9 @@
 """DNA k = 14..16 in key-range passes at a cfg3-shaped share (16 groups x 2 matrices x 10 000 sites, alpha 0.05): per pass the
 scoring, reduce and key-major writer times, keys and entries, the shard file's seconds; the merge of the pass files; device
 memory in use after a pass' scoring.  k = 14 as one call beside its 4 passes gives the cost of rebuilding the right halves in
-every pass.  Usage: python tools/keyrange_probe.py [groups] [sites] [out.txt] [alpha]"""
+every pass.  slice = 1 sets the engine option "slice_long_lists" (windows whose half lists exceed the big-list cap are scored in
+slices instead of failing the pass) and reports the windows sliced per case; cases: a comma-separated subset of
+one14,14x4,15x4,15x16,16x16.  Usage: python tools/keyrange_probe.py [groups] [sites] [out.txt] [alpha] [slice] [cases]"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,6 +17,8 @@ groups = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 sites = int(sys.argv[2]) if len(sys.argv) > 2 else 10000
 out_path = sys.argv[3] if len(sys.argv) > 3 else None
 alpha = float(sys.argv[4]) if len(sys.argv) > 4 else 0.05
+slice_on = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+only = sys.argv[6].split(",") if len(sys.argv) > 6 else None
 lines = []
 
 
@@ -27,8 +31,10 @@ mats = synth_matrices(2 * groups, sites, 4, alpha, 42)
 mg = np.repeat(np.arange(groups, dtype=np.uint32), 2)
 dev = torch.from_numpy(mats).cuda()
 eng = ipk_amd.Engine(0)
+if slice_on:
+    eng.set_option("slice_long_lists", 1)
 free0, total = torch.cuda.mem_get_info()
-say(f"keyrange probe: {groups} groups x 2 matrices x {sites} sites, alpha {alpha}, omega 1.5, mif0 filter, device writer; "
+say(f"keyrange probe: {groups} groups x 2 matrices x {sites} sites, alpha {alpha}, omega 1.5, mif0 filter, device writer, slice_long_lists {slice_on}; "
     f"device memory in use before: {(total - free0) / 2**30:.2f} GiB")
 work = tempfile.mkdtemp(prefix="kr_probe_")
 hdr = ([(1, 0.0)] * (groups + 1), "a;")
@@ -83,9 +89,24 @@ def passes(k, n):
         f"entries per pass {min(p['entries'] for p in pp)}..{max(p['entries'] for p in pp)}")
 
 
+def sliced_windows():
+    try:
+        return eng.get_option("debug_sliced_windows")
+    except ipk_amd.IpkGpuError:
+        return 0
+
+
 for case in (("one", 14), ("passes", 14, 4), ("passes", 15, 4), ("passes", 15, 16), ("passes", 16, 16)):
+    name = "one14" if case[0] == "one" else f"{case[1]}x{case[2]}"
+    if only and name not in only:
+        continue
+    before = sliced_windows()
     try:
         one_call(case[1]) if case[0] == "one" else passes(case[1], case[2])
+        if slice_on:
+            # (every build of a case runs twice, and a window is counted once per pass that meets it)
+            say(f"    windows scored in slices, summed over the case's {2 if case[0] == 'one' else 2 * case[2]} scoring calls: {sliced_windows() - before} "
+                f"of {groups * 2 * (sites - case[1] + 1)} windows a call")
     except ipk_amd.IpkGpuError as e:
         say(f"{case}: {e}")
 eng.close()
