@@ -354,7 +354,7 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
  * the budget leaves.  The context stays usable after such a failure.  Device memory of the caller (the matrices) is not counted. */
 int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak);
 /* Reads back "workspace_bytes", "device_budget_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
- * "debug_sliced_windows" (the windows this context has scored in slices so far), or "last_refused_bytes":
+ * "debug_sliced_windows" (the windows this context has scored in slices so far), "debug_pool_bytes" (the bytes its pair pool holds), or "last_refused_bytes":
  * the bytes held plus the size of the last allocation the device or the budget refused -- what the failed step needed at least.
  * IPKGPU_ERR_INVALID for other names. */
 int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value);

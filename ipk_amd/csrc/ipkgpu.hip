@@ -632,19 +632,23 @@ int launch_stream_pass1(ipkgpu_ctx* ctx, const StreamParams& sp, uint32_t n_wg)
     }
 }
 
-template <int SIGMA, int K>
+// LAYOUT: the layout of the pool the big-list windows join (Pass::layout)
+template <int SIGMA, int K, PairLayout LAYOUT = PairLayout::PAIR8>
 int launch_stream_overflow(ipkgpu_ctx* ctx, const StreamParams& sp)
 {
     constexpr uint32_t TBL = stream_tbl<SIGMA, K>();
     if constexpr (TBL == 0 || ipow(SIGMA, K - K / 2) <= (uint32_t)fast_cap<SIGMA, K>()) {
         (void)ctx; (void)sp;
         return IPKGPU_OK;                           // lists can never overflow
+    } else if constexpr (LAYOUT != PairLayout::PAIR8 && (TBL & (TBL - 1)) != 0) {
+        (void)sp;
+        return fail(ctx, IPKGPU_ERR_INVALID, "no 6-byte pair layout for this sigma/k");
     } else {
         constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
         constexpr size_t lds = TileGeo<SIGMA, K, 1>::HEAD_BYTES + (size_t)wave_scratch_entries<SIGMA, K, big_capf<SIGMA, K>()>() * 8 +
                                (size_t)OVF_NW * 2 * NB * SUB * 4;
         static_assert(lds + 64 <= 160 * 1024, "big-list (stream) LDS budget");
-        auto kern = score_overflow_stream_kernel<SIGMA, K, TBL>;
+        auto kern = score_overflow_stream_kernel<SIGMA, K, TBL, LAYOUT>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(32 / OVF_NW, (160 * 1024) / (lds + 64)));
@@ -660,11 +664,13 @@ int launch_stream_overflow(ipkgpu_ctx* ctx, const StreamParams& sp)
 #ifndef IPK_RPIPE_D
 #define IPK_RPIPE_D 2            // chunks per trip of the persistent reduce (two trips of D * 4 eight-byte loads per lane in flight)
 #endif
+template <int SIGMA, int K> constexpr PairLayout quad_layout();
+// layout: the layout pass 1 gave the pool (Pass::layout)
 template <int SIGMA, int K>
-int launch_stream_pass2(ipkgpu_ctx* ctx, uint32_t n_gb, uint64_t T, uint32_t* table, bool compress)
+int launch_stream_pass2(ipkgpu_ctx* ctx, uint32_t n_gb, uint64_t T, uint32_t* table, bool compress, PairLayout layout)
 {
     constexpr uint32_t TBL = stream_tbl<SIGMA, K>();
-    if constexpr (TBL == 0) { (void)n_gb; (void)T; (void)table; (void)compress; return fail(ctx, IPKGPU_ERR_INVALID, "stream variant unsupported"); }
+    if constexpr (TBL == 0) { (void)n_gb; (void)T; (void)table; (void)compress; (void)layout; return fail(ctx, IPKGPU_ERR_INVALID, "stream variant unsupported"); }
     else {
         constexpr uint32_t NB = (uint32_t)((ipow(SIGMA, K) + TBL - 1) / TBL);
         constexpr int NT = TBL <= 16384 ? 512 : 1024;
@@ -682,7 +688,7 @@ int launch_stream_pass2(ipkgpu_ctx* ctx, uint32_t n_gb, uint64_t T, uint32_t* ta
         // share: 2.72-2.85 ms against 3.03-3.07 for the workgroup-per-slice kernel); debug_flags bit 11 switches to the other of the
         // two (tests compare them)
         if constexpr (TBL * 4 > 80 * 1024) {
-            if (compress && ((IPK_RPIPE_DEFAULT != 0) != ((ctx->opt_flags & 2048) != 0))) {
+            if (layout == PairLayout::PAIR8 && compress && ((IPK_RPIPE_DEFAULT != 0) != ((ctx->opt_flags & 2048) != 0))) {
                 constexpr int PD = IPK_RPIPE_D;
                 auto kern = reduce_buckets_pipe_kernel<TBL, NT, PD>;
                 HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -692,6 +698,13 @@ int launch_stream_pass2(ipkgpu_ctx* ctx, uint32_t n_gb, uint64_t T, uint32_t* ta
                 HIP_TRY(ctx, hipGetLastError());
                 return IPKGPU_OK;
             }
+        }
+        if (layout == PairLayout::PAIR6) {
+            // (the one (sigma, k) family whose pass 1 writes the layout: no other instantiation of the PAIR6 reduce exists)
+            if constexpr (quad_layout<SIGMA, K>() == PairLayout::PAIR6)
+                return compress ? launch(reduce_buckets_kernel<TBL, NT, true, PairLayout::PAIR6>) : launch(reduce_buckets_kernel<TBL, NT, false, PairLayout::PAIR6>);
+            else
+                return fail(ctx, IPKGPU_ERR_INVALID, "no 6-byte pair layout for this sigma/k");
         }
         return compress ? launch(reduce_buckets_kernel<TBL, NT, true>) : launch(reduce_buckets_kernel<TBL, NT, false>);
     }
@@ -736,6 +749,15 @@ template <int SIGMA, int K> constexpr bool quad_rowlane() { return K <= 10 ? IPK
 #define IPK_QONEWIN12 1
 #endif
 template <int SIGMA, int K> constexpr bool quad_onewin() { return K >= 11 && IPK_QONEWIN12 != 0 && quad_rowlane<SIGMA, K>(); }
+// the pool layout of a pass whose pass 1 is the quad kernel: 6-byte pairs in two planes behind the candidate-per-lane join
+// (k = 8..10), 8-byte pairs behind the row-per-lane join (kernels_score.hpp ChunkLayout; -DIPK_PAIR6=0: 8-byte pairs everywhere)
+#ifndef IPK_PAIR6
+#define IPK_PAIR6 1
+#endif
+template <int SIGMA, int K> constexpr PairLayout quad_layout()
+{
+    return IPK_PAIR6 != 0 && quad_ok<SIGMA, K>() && K <= 10 && !quad_rowlane<SIGMA, K>() ? PairLayout::PAIR6 : PairLayout::PAIR8;
+}
 template <int SIGMA, int K> size_t quad_lds()
 {
     if constexpr (!quad_ok<SIGMA, K>()) return 0;
@@ -748,15 +770,16 @@ template <int SIGMA, int K> size_t quad_lds()
     }
 }
 template <int SIGMA, int K, bool COUNT_ONLY = false>
-int launch_quad_pass1(ipkgpu_ctx* ctx, const StreamParams& sp, uint32_t n_wg)
+int launch_quad_pass1(ipkgpu_ctx* ctx, const StreamParams& sp, uint32_t n_wg, PairLayout layout)
 {
-    if constexpr (!quad_ok<SIGMA, K>()) { (void)sp; (void)n_wg; return fail(ctx, IPKGPU_ERR_INVALID, "quad kernel unsupported for this sigma/k"); }
+    if constexpr (!quad_ok<SIGMA, K>()) { (void)sp; (void)n_wg; (void)layout; return fail(ctx, IPKGPU_ERR_INVALID, "quad kernel unsupported for this sigma/k"); }
     else {
+        if (layout != quad_layout<SIGMA, K>()) return fail(ctx, IPKGPU_ERR_INVALID, "the pass' pool layout is not the quad kernel's");
         constexpr int CAP = fast_cap<SIGMA, K>();
         constexpr uint32_t TBL = stream_tbl<SIGMA, K>();
         constexpr int QNW = quad_nw<SIGMA, K>(), QTW = quad_tw<SIGMA, K>();
         const size_t lds = quad_lds<SIGMA, K>();
-        auto kern = score_quad_kernel<SIGMA, K, CAP, QTW, QNW, TBL, COUNT_ONLY, quad_rowlane<SIGMA, K>(), quad_onewin<SIGMA, K>()>;
+        auto kern = score_quad_kernel<SIGMA, K, CAP, QTW, QNW, TBL, COUNT_ONLY, quad_rowlane<SIGMA, K>(), quad_onewin<SIGMA, K>(), quad_layout<SIGMA, K>()>;
         if (lds > 64 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(n_wg), dim3(QNW * 64), lds, ctx->stream, sp);
@@ -922,6 +945,7 @@ struct Geometry {
     bool quad = false;                             // the quad kernel (pass 1 of the stream variant) exists
     uint32_t quad_nw = NW, quad_tw = TW;
     size_t quad_lds = 0;
+    PairLayout quad_layout = PairLayout::PAIR8;    // the pool layout its final join writes
     uint32_t xp_nb = 0, xp_tbl = 0;                // exact partition: key buckets per group, slots per bucket (0: none)
     size_t xp_lds = 0;
 };
@@ -935,6 +959,7 @@ int fill_geometry(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t lead, Ge
             g.stream_nw = stream_nw<S_, K_>(); g.stream_tw = stream_tw<S_, K_>(); g.stream_lds = stream_lds<S_, K_>();
             g.quad = quad_ok<S_, K_>();
             g.quad_nw = quad_nw<S_, K_>(); g.quad_tw = quad_tw<S_, K_>(); g.quad_lds = quad_lds<S_, K_>();
+            g.quad_layout = quad_layout<S_, K_>();
             return IPKGPU_OK;
         }));
     return with_xp_shape(ctx, sigma, k, lead, [&](auto S_, auto K_, auto KK_) {
@@ -991,6 +1016,8 @@ struct Pass {
     bool positions = false;            // tiles kernel with 8-byte (score, position) table entries
     bool compress = false;             // compressed tables: the exact partition's, or where the stream variant must take them
     bool seq = false;                  // positioned key-major call: the exact partition's pairs carry their windows' sequence numbers
+    PairLayout layout = PairLayout::PAIR8;   // stream variant: the chunk layout of the pass' pair pool -- set here with the pass-1 kernel, read by
+                                       // the pool's sizing, every kernel that appends to the pool and the reduce
     double slot_bytes() const { return positions ? 8.0 : kind == PassKind::xp && compress ? 0.3125 : 4.0; }
 };
 
@@ -1006,6 +1033,7 @@ Pass choose_pass(int64_t variant, uint32_t sigma, uint32_t lead, bool positions,
         ps.compress = v != 3;
     } else if (g.stream_nb != 0 && g.stream_nb <= 2048 && (v == 0 || v == 2 || v == 5 || v == 6 || v == 7)) {
         ps.kind = v != 2 && g.quad ? PassKind::quad : PassKind::stream;
+        ps.layout = ps.kind == PassKind::quad ? g.quad_layout : PairLayout::PAIR8;
         // DNA k = 11, 12 by default (cfg3: 38 % of 4^12 slots per group -- no 64 MB dense table per group to write and read back)
         ps.compress = v == 6 || (v == 0 && g.stream_tbl == 32768u && sigma == 4);
     }
@@ -1395,7 +1423,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     auto pass1 = [&](const StreamParams& sp, uint32_t n_wg, bool count_only) {
         return with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
             if (!use_quad) return launch_stream_pass1<S_, K_>(ctx, sp, n_wg);
-            return count_only ? launch_quad_pass1<S_, K_, true>(ctx, sp, n_wg) : launch_quad_pass1<S_, K_, false>(ctx, sp, n_wg);
+            return count_only ? launch_quad_pass1<S_, K_, true>(ctx, sp, n_wg, ps.layout) : launch_quad_pass1<S_, K_, false>(ctx, sp, n_wg, ps.layout);
         });
     };
 
@@ -1454,6 +1482,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     const uint64_t wg_per_cu = std::max<uint64_t>(1, std::min<uint64_t>(32 / SNW, (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
     const uint64_t slots = (uint64_t)ctx->num_cu * wg_per_cu;
     const uint32_t CH = chunk_pairs_rt(TBL);      // pairs per chunk of this (sigma, k)
+    const uint64_t CHB = chunk_bytes_rt(TBL, ps.layout);   // ... and its bytes in the pass' layout
     const uint64_t expected_chunks = (uint64_t)((double)windows * ppw_est / CH);
 #ifndef IPK_WG_CHUNKS2
 #define IPK_WG_CHUNKS2 2      // a wavefront should fill at least IPK_WG_CHUNKS2 / 2 chunks per bucket (4: +3.5 % at a 125-group share of cfg2)
@@ -1472,8 +1501,8 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     const uint64_t n_gb = (uint64_t)gb * NBK;
 
     const size_t free_b = mem_free_bytes(ctx);
-    uint64_t max_chunks = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)(free_b + ctx->pool.cap + ctx->desc.cap) * 9 / 10 / (CH * 8 + 8));
-    if (ctx->opt_pool_limit > 0) max_chunks = std::min<uint64_t>(max_chunks, (uint64_t)ctx->opt_pool_limit / (CH * 8 + 8));
+    uint64_t max_chunks = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)(free_b + ctx->pool.cap + ctx->desc.cap) * 9 / 10 / (CHB + 8));
+    if (ctx->opt_pool_limit > 0) max_chunks = std::min<uint64_t>(max_chunks, (uint64_t)ctx->opt_pool_limit / (CHB + 8));
     // pool size: pairs expected (calibrated by the previous call, +25 %) plus every wave's open chunks and id batches.
     // An existing pool is kept as long as it covers the expectation without the margin -- regrowing a multi-GB
     // buffer costs hundreds of ms, and an underestimate is caught by the redo path anyway.
@@ -1483,7 +1512,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
     uint64_t want = (uint64_t)((double)windows * ppw * 1.25 / CH) + slack;
     {
         // (the pool holds one spare chunk past its last id: kernels_quad.hpp, RowAppender)
-        const uint64_t have = std::min<uint64_t>(std::max<uint64_t>(ctx->pool.cap / (CH * 8), 1) - 1, ctx->desc.cap / 8);
+        const uint64_t have = std::min<uint64_t>(std::max<uint64_t>(ctx->pool.cap / CHB, 1) - 1, ctx->desc.cap / 8);
         // expectation without the safety margins: pairs +10 %, ONE open chunk per (wave, bucket), the id batches
         const uint64_t need = (uint64_t)((double)windows * ppw * 1.1 / CH) + (n_waves + ovf_waves) * (NBK * SUB + ALLOC_BATCH) + 1024;
         if (have >= need) want = have;
@@ -1497,9 +1526,9 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
             if (gb > 1) return IPKGPU_RETRY_SMALLER;
             return fail(ctx, IPKGPU_ERR_NOMEM, "the pair pool of ONE branch group does not fit device memory");
         }
-        RC_TRY(ensure(ctx, ctx->pool, (cap + 1) * CH * 8));
+        RC_TRY(ensure(ctx, ctx->pool, (cap + 1) * CHB));
         RC_TRY(ensure(ctx, ctx->desc, cap * 8));
-        if (!forced) cap = std::min<uint64_t>(ctx->pool.cap / (CH * 8) - 1, ctx->desc.cap / 8);
+        if (!forced) cap = std::min<uint64_t>(ctx->pool.cap / CHB - 1, ctx->desc.cap / 8);
         RC_TRY(ensure(ctx, ctx->gbcnt, 2 * n_gb * 4));             // [chunks per (group, bucket) | scatter cursors]: one fill for both
         uint32_t* const d_gbcur = ctx->gbcnt.as<uint32_t>() + n_gb;
         RC_TRY(ensure(ctx, ctx->gboff, (n_gb + 1) * 8));
@@ -1576,7 +1605,11 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
             so.ovf_queue = ctx->tmp_b.as<unsigned long long>();
             // with the quad kernel the pool's pairs are counted from the chunk descriptors: the big-list kernel's own count goes nowhere
             if (use_quad) so.emitted = small_at<unsigned long long>(ctx, SMALL_OVF_EMITTED);
-            RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) { return launch_stream_overflow<S_, K_>(ctx, so); }));
+            RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
+                if constexpr (quad_layout<S_, K_>() == PairLayout::PAIR6) { if (ps.layout == PairLayout::PAIR6) return launch_stream_overflow<S_, K_, PairLayout::PAIR6>(ctx, so); }
+                if (ps.layout != PairLayout::PAIR8) return fail(ctx, IPKGPU_ERR_INVALID, "no big-list kernel for the pass' pool layout");
+                return launch_stream_overflow<S_, K_>(ctx, so);
+            }));
         }
         if (ovf_in_pool) {
             HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rb, ctx->small, SMALL_BYTES, hipMemcpyDeviceToHost, ctx->stream));
@@ -1635,7 +1668,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         }
         const int ev_c = sw.mark();
         RC_TRY(with_sigma_k(ctx, pl.sigma, pl.k, [&](auto S_, auto K_) {
-            return launch_stream_pass2<S_, K_>(ctx, (uint32_t)n_gb, pl.table_size, ctx->table.as<uint32_t>(), s_compress);
+            return launch_stream_pass2<S_, K_>(ctx, (uint32_t)n_gb, pl.table_size, ctx->table.as<uint32_t>(), s_compress, ps.layout);
         }));
         const int ev_d = sw.mark();
         if ((spec || n_ovf > 0) && !ovf_in_pool)
@@ -3085,6 +3118,7 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
     if (!strcmp(name, "slice_long_lists")) { *value = ctx->opt_slice; return IPKGPU_OK; }
     if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
+    if (!strcmp(name, "debug_pool_bytes")) { *value = (int64_t)ctx->pool.cap; return IPKGPU_OK; }   // bytes the pair pool holds (tests)
     return IPKGPU_ERR_INVALID;
 }
 

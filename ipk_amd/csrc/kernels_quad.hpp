@@ -192,6 +192,43 @@ __device__ __forceinline__ uint64_t pool_store_inside(uint2* wave_base, uint32_t
     return outside;
 }
 
+
+// ---- the same stores into a PAIR6 chunk (ChunkLayout): the score into the f32 plane at `where + 4 v`, the key's low half into the
+// u16 plane at `where + 2 v` + 4 * CH (the plane's offset rides in the store's immediate field).  off4 / off2 are those two
+// offsets; the low 16 bits of the key hold its slot in the bucket's table (the reduce masks with TBL - 1).
+template <uint32_t SLOT_PLANE>
+__device__ __forceinline__ void pool_store6(uint2* wave_base, uint32_t off4, uint32_t off2, uint2 val)
+{
+    static_assert(SLOT_PLANE < 4096, "the slot plane's offset must fit the store's immediate field");
+    asm volatile("global_store_dword %0, %2, %4\n\tglobal_store_short %1, %3, %4 offset:%5"
+                 : : "v"(off4), "v"(off2), "v"(val.y), "v"(val.x), "s"(wave_base), "n"(SLOT_PLANE) : "memory");
+}
+// (x << SH) + y as ONE instruction, as lshl3_add
+template <int SH>
+__device__ __forceinline__ uint32_t lshl_add(uint32_t x, uint32_t y)
+{
+    uint32_t r;
+    asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(r) : "v"(x), "v"(y), "n"(SH));
+    return r;
+}
+// pool_store_inside for a PAIR6 chunk: both stores inside the one exec region.  From code that runs with ALL lanes enabled.
+template <uint32_t SLOT_PLANE>
+__device__ __forceinline__ uint64_t pool_store_inside6(uint2* wave_base, uint32_t off4, uint32_t off2, uint2 val, uint32_t v, uint64_t pass, uint32_t CH)
+{
+    static_assert(SLOT_PLANE < 4096, "the slot plane's offset must fit the store's immediate field");
+    uint64_t outside;
+    IPK_ASSERT_FULL_EXEC();
+    asm volatile("s_mov_b64 exec, %7\n\t"
+                 "v_cmpx_gt_u32_e32 vcc, %8, %6\n\t"
+                 "global_store_dword %1, %3, %5\n\t"
+                 "global_store_short %2, %4, %5 offset:%9\n\t"
+                 "s_andn2_b64 %0, %7, exec\n\t"
+                 "s_mov_b64 exec, -1"
+                 : "=&s"(outside) : "v"(off4), "v"(off2), "v"(val.y), "v"(val.x), "s"(wave_base), "v"(v), "s"(pass), "s"(CH), "n"(SLOT_PLANE)
+                 : "memory", "vcc");
+    return outside;
+}
+
 constexpr uint32_t QUAD_SPAN_BYTES_LOG2 = 32;       // a wavefront's open chunks stay within 4 GiB of its base chunk
 constexpr uint32_t QUAD_SPAN_TEST = 8;            // debug_flags bit 3: rebase every 8 chunks (tests of the rebasing path)
 
@@ -207,22 +244,23 @@ __device__ __forceinline__ uint32_t div_small(float x_plus_half, float rn) { ret
 // its life.  When a new chunk lies 4 GiB or more past the base (or the pool is exhausted: then the "chunk" is the spare one at
 // id pool_cap, which absorbs the stores of a launch that is going to be repeated with a bigger pool), every open chunk is
 // closed as it is -- a descriptor may hold any count <= CH -- and the new chunk becomes the base.
-template <uint32_t NB, uint32_t CH>
+template <uint32_t NB, uint32_t CH, uint32_t PAIR_BYTES = 8u>
 struct RowAppender {
     static constexpr uint32_t NONE = 0xFFFFFFFFu;
-    static constexpr uint32_t CHUNK_BYTES = CH * 8u;
+    static constexpr uint32_t CHUNK_BYTES = CH * PAIR_BYTES;     // ChunkLayout<TBL, LAYOUT>::BYTES
     static constexpr uint32_t SPAN_CHUNKS = (uint32_t)((1ull << QUAD_SPAN_BYTES_LOG2) / CHUNK_BYTES);
     const StreamParams& p;
     unsigned long long* st;                 // [NB]
     uint32_t g;
     uint32_t chunk_next = 0, chunk_end = 0;
     uint32_t base_id = 0;
-    uint2* base = nullptr;                  // p.pool + base_id * CH
+    uint2* base = nullptr;                  // the pool's byte base_id * CHUNK_BYTES
 
-    // wave_gid: this wavefront's number in the launch.  With pre-assigned first chunks (p.pre_chunks; the host grants them only while
-    // the whole pool lies within one store window of 4 GiB, so that no rebase can follow) bucket b starts, empty, in chunk
-    // wave_gid * NB + b and that chunk is the base: a wavefront's first touch of each of its buckets is then no chunk roll --
-    // 40 % of all rolls at cfg2, more for a rank's share.
+    // wave_gid: this wavefront's number in the launch.  With pre-assigned first chunks (p.pre_chunks; the host grants them wherever
+    // the pool has room for them, whatever its size) bucket b starts, empty, in chunk wave_gid * NB + b and that chunk is the base: a
+    // wavefront's first touch of each of its buckets is then no chunk roll -- 40 % of all rolls at cfg2, more for a rank's share.
+    // In a pool beyond the 4-GiB store window the first chunk the wavefront DRAWS usually lies outside the window of that base: it
+    // rebases once, by which time its buckets have filled most of their first chunks.
     __device__ __forceinline__ void init(uint32_t wave_gid)
     {
         const uint32_t first = wave_gid * NB;
@@ -232,7 +270,7 @@ struct RowAppender {
         base = p.pool;
         if (pre) {
             base_id = first;
-            const unsigned long long a = (unsigned long long)(p.pool + (size_t)first * CH);
+            const unsigned long long a = (unsigned long long)p.pool + (unsigned long long)first * CHUNK_BYTES;
             base = reinterpret_cast<uint2*>(((unsigned long long)to_sgpr((uint32_t)(a >> 32)) << 32) | to_sgpr((uint32_t)a));
         }
     }
@@ -253,7 +291,7 @@ struct RowAppender {
         }
         wave_lds_sync();
         base_id = nid;
-        const unsigned long long a = (unsigned long long)(p.pool + (size_t)nid * CH);
+        const unsigned long long a = (unsigned long long)p.pool + (unsigned long long)nid * CHUNK_BYTES;
         base = reinterpret_cast<uint2*>(((unsigned long long)to_sgpr((uint32_t)(a >> 32)) << 32) | to_sgpr((uint32_t)a));
     }
     // bucket b's chunk is full: close it, open a new one; returns the new chunk's byte offset from `base`
@@ -381,7 +419,11 @@ __device__ __forceinline__ void store_pair_if_gt(unsigned long long& cursor, uin
 // instead of two nodes of two windows: the same number of steps per window at k = 12 (all four nodes have three symbols), but
 // only one window's child lists are alive at a time -- 2 KB less LDS per wavefront, which with 32-window tiles and half-list
 // capacity 384 admits a fourth workgroup per CU (12 wavefronts instead of 9).
-template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool COUNT_ONLY = false, bool ROWLANE = false, bool ONEWIN = false>
+//
+// LAYOUT: the pool's chunk layout (kernels_score.hpp ChunkLayout).  PAIR6 exists for the candidate-per-lane join only; the
+// row-per-lane join's lanes walk their runs with 8-byte cursors and stay on PAIR8.
+template <int SIGMA, int K, int CAP, int TW, int NW, uint32_t TBL, bool COUNT_ONLY = false, bool ROWLANE = false, bool ONEWIN = false,
+          PairLayout LAYOUT = PairLayout::PAIR8>
 __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -393,6 +435,9 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
     constexpr uint32_t CH = chunk_pairs<TBL>();
     constexpr uint32_t mulR = Q::mulR;
     static_assert(TBL % mulR == 0, "a row of the final join must stay inside one bucket");
+    using CL = ChunkLayout<TBL, LAYOUT>;
+    static_assert(!ROWLANE || LAYOUT == PairLayout::PAIR8, "the row-per-lane join writes 8-byte pairs");
+    constexpr bool P6 = LAYOUT == PairLayout::PAIR6;
     constexpr uint32_t CAPL = Geo<SIGMA, Q::HL, CAP>::CAPH, CAPR = Geo<SIGMA, Q::HR, CAP>::CAPH;
     constexpr uint32_t WS = quad_wave_entries<SIGMA, K, CAP, ONEWIN>();
     constexpr uint32_t WPW = ONEWIN ? 1u : 2u;                     // windows per wavefront step
@@ -414,7 +459,7 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
     uint2* child = scratch_all + (size_t)wave * WS;                // [WPW][CW]
     uint2* lp = child + WPW * Q::CW;                               // L list (codes already multiplied by mulR)
     uint2* rp = lp + CAPL;                                         // R list
-    using Appender = std::conditional_t<ROWLANE, LaneAppender<NB, CH>, RowAppender<NB, CH>>;
+    using Appender = std::conditional_t<ROWLANE, LaneAppender<NB, CH>, RowAppender<NB, CH, CL::PAIR_BYTES>>;
     Appender app{p, state_all + (size_t)wave * NB, g};
     app.init(blockIdx.x * NW + wave);
     unsigned long long emitted = 0;
@@ -744,7 +789,10 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
                             const uint32_t where = (uint32_t)__builtin_amdgcn_ds_bpermute(head_addr, (int)(uint32_t)(got[u] >> 32));
                             v[u] = fill + rank[u];
                             val[u] = make_uint2(a[u].x + b.x, __float_as_uint(s[u]));
-                            ovf[u] = pool_store_inside(app.base, lshl3_add(v[u], where), val[u], v[u], m[u], CH);
+                            if constexpr (P6)
+                                ovf[u] = pool_store_inside6<CL::SLOT_PLANE>(app.base, lshl_add<2>(v[u], where), lshl_add<1>(v[u], where), val[u], v[u], m[u], CH);
+                            else
+                                ovf[u] = pool_store_inside(app.base, lshl3_add(v[u], where), val[u], v[u], m[u], CH);
                             anyo |= ovf[u];
                         }
                         while (anyo) {                                                // a bucket's chunk filled up: open a new one
@@ -758,7 +806,8 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
 #pragma unroll
                             for (int u = 0; u < NS; ++u) {
                                 const bool h = ((ovf[u] >> lane) & 1ull) != 0 && bk[u] == bb;
-                                if (h) pool_store(app.base, nwhere + ((v[u] - CH) << 3), val[u]);
+                                if constexpr (P6) { if (h) pool_store6<CL::SLOT_PLANE>(app.base, nwhere + ((v[u] - CH) << 2), nwhere + ((v[u] - CH) << 1), val[u]); }
+                                else if (h) pool_store(app.base, nwhere + ((v[u] - CH) << 3), val[u]);
                                 ovf[u] &= ~ballot64(h);
                                 anyo |= ovf[u];
                             }

@@ -493,6 +493,25 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_kernel(ScoreParams
 #endif
 template <uint32_t TBL> constexpr uint32_t chunk_pairs() { return (TBL == 16384 || TBL == IPK_CH512_TBL) ? 512u : 256u; }
 inline uint32_t chunk_pairs_rt(uint32_t tbl) { return (tbl == 16384 || tbl == IPK_CH512_TBL) ? 512u : 256u; }
+// How a chunk's CH pairs lie in its bytes.  A chunk belongs to one (group, bucket) and its descriptor names the bucket, so inside
+// the chunk a key needs only its slot in the bucket's table -- log2(TBL) bits.
+//   PAIR8   uint2 (dense key, score bits)[CH]: 8 bytes per pair
+//   PAIR6   two planes: f32 score[CH] at byte 0, u16 slot[CH] at byte 4 * CH, slot = key - bucket * TBL: 6 bytes per pair
+//           (the candidate-per-lane quad kernel, DNA k = 8..10, and the reduce behind it: a quarter fewer bytes through both)
+// Pairs per chunk, descriptors, chunk index and ALLOC_BATCH are the same for both; only a chunk's byte size and what a producer
+// stores / the reduce loads differ.  Chunk `id` starts at byte id * BYTES of the pool.
+enum class PairLayout : uint32_t { PAIR8 = 0, PAIR6 = 1 };
+template <uint32_t TBL, PairLayout L>
+struct ChunkLayout {
+    static_assert(TBL <= 65536, "a slot of the bucket's table must fit the u16 plane");
+    static_assert(L == PairLayout::PAIR8 || (TBL & (TBL - 1)) == 0, "PAIR6: slot = key mod TBL is taken from the key's low bits");
+    static constexpr uint32_t CH = chunk_pairs<TBL>();
+    static constexpr uint32_t PAIR_BYTES = L == PairLayout::PAIR6 ? 6u : 8u;
+    static constexpr uint32_t BYTES = PAIR_BYTES * CH;
+    static constexpr uint32_t SLOT_PLANE = 4u * CH;                // PAIR6: byte offset of the u16 plane
+    static_assert(BYTES % 128 == 0, "chunks start on cache-line boundaries");
+};
+inline uint32_t chunk_bytes_rt(uint32_t tbl, PairLayout l) { return (l == PairLayout::PAIR6 ? 6u : 8u) * chunk_pairs_rt(tbl); }
 constexpr uint32_t CHUNK_NONE = 0xFFFFFFFFu;
 constexpr uint32_t ALLOC_BATCH = 32;         // chunk ids a wavefront draws per global atomic
 constexpr uint32_t SUB = 1;                  // open chunks per (wave, bucket); >1 spreads a bucket over lane-interleaved chunks
@@ -505,7 +524,7 @@ struct StreamParams {
     uint32_t sites, nwin, tiles_per_mat, S;   // S = segments (workgroups) per group
     float eps;
     uint32_t slice_lists = 0;      // capped lists: as ScoreParams::slice_lists (in the padding behind eps: no offset moves)
-    uint2* pool;                   // [pool_cap][chunk_pairs<TBL>()] pairs (dense code, score bits)
+    uint2* pool;                   // [pool_cap + 1] chunks of chunk_pairs<TBL>() pairs in the pass' layout (ChunkLayout; PAIR8: (dense code, score bits))
     uint32_t pool_cap;
     uint32_t* pool_next;           // next free chunk
     unsigned long long* desc;      // [pool_cap] (group * NB + bucket) << 32 | count ; 0 = unused
@@ -627,9 +646,10 @@ __device__ __forceinline__ bool build_halves_dd(const WinCtx& c, float eps, uint
 }
 
 // Per-wave appender of surviving (code, score) pairs to the pair pool: one open chunk per key bucket.
-template <uint32_t TBL, uint32_t NB>
+template <uint32_t TBL, uint32_t NB, PairLayout LAYOUT = PairLayout::PAIR8>
 struct Appender {
     static constexpr uint32_t CH = chunk_pairs<TBL>();
+    using CL = ChunkLayout<TBL, LAYOUT>;
     const StreamParams& p;
     uint32_t* cbase;
     uint32_t* cfill;
@@ -663,6 +683,17 @@ struct Appender {
         return nid;
     }
 
+    // pair (idx, sb) into slot `slot` of chunk `id`, in the pool's layout
+    __device__ __forceinline__ void put(uint32_t id, uint32_t slot, uint32_t idx, uint32_t sb)
+    {
+        if constexpr (LAYOUT == PairLayout::PAIR8) p.pool[(size_t)id * CH + slot] = make_uint2(idx, sb);
+        else {
+            unsigned char* c = reinterpret_cast<unsigned char*>(p.pool) + (size_t)id * CL::BYTES;
+            reinterpret_cast<uint32_t*>(c)[slot] = sb;
+            reinterpret_cast<unsigned short*>(c + CL::SLOT_PLANE)[slot] = (unsigned short)idx;     // (low bits of the key: its slot in the bucket)
+        }
+    }
+
     // Two candidates per lane (two steps of the final join): slots are reserved with LDS atomics, both
     // reservations in flight together.  (Ballot-ranked variants without same-address atomics were
     // measured 40-55 % slower: the extra 64-bit lane masks push the kernel into SGPR spilling.)
@@ -676,8 +707,8 @@ struct Appender {
         if (pass0) cb0 = cbase[bk0];
         if (pass1) cb1 = cbase[bk1];
         const bool st = !(p.flags & 1u);
-        if (pass0 && slot0 < CH && cb0 != CHUNK_NONE && st) p.pool[(size_t)cb0 * CH + slot0] = make_uint2(idx0, sb0);
-        if (pass1 && slot1 < CH && cb1 != CHUNK_NONE && st) p.pool[(size_t)cb1 * CH + slot1] = make_uint2(idx1, sb1);
+        if (pass0 && slot0 < CH && cb0 != CHUNK_NONE && st) put(cb0, slot0, idx0, sb0);
+        if (pass1 && slot1 < CH && cb1 != CHUNK_NONE && st) put(cb1, slot1, idx1, sb1);
         const bool o0 = pass0 && slot0 >= CH, o1 = pass1 && slot1 >= CH;
         uint64_t ovf0 = __ballot(o0), ovf1 = __ballot(o1);
         while (ovf0 | ovf1) {                           // a bucket's chunk filled up: open a new one
@@ -687,8 +718,8 @@ struct Appender {
             const bool h0 = o0 && bk0 == bb, h1 = o1 && bk1 == bb;
             const uint64_t m0 = __ballot(h0), m1 = __ballot(h1);
             const uint32_t nid = roll(bb);
-            if (h0 && nid != CHUNK_NONE && st) p.pool[(size_t)nid * CH + (slot0 - CH)] = make_uint2(idx0, sb0);
-            if (h1 && nid != CHUNK_NONE && st) p.pool[(size_t)nid * CH + (slot1 - CH)] = make_uint2(idx1, sb1);
+            if (h0 && nid != CHUNK_NONE && st) put(nid, slot0 - CH, idx0, sb0);
+            if (h1 && nid != CHUNK_NONE && st) put(nid, slot1 - CH, idx1, sb1);
             ovf0 &= ~m0; ovf1 &= ~m1;
         }
     }
@@ -816,8 +847,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(80))) void 
 // the half lists at worst-case capacity, all waves share the final cross product), but the survivors are
 // appended to the pair pool like everything else, so they are max-reduced in LDS by pass 2 instead of by
 // global atomics.  Runs between pass 1 and the chunk index.  A wave keeps its chunks open while
-// consecutive queue entries belong to the same group.
-template <int SIGMA, int K, uint32_t TBL>
+// consecutive queue entries belong to the same group.  LAYOUT: the layout of the pool it joins (the pass-1 kernel's).
+template <int SIGMA, int K, uint32_t TBL, PairLayout LAYOUT = PairLayout::PAIR8>
 __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_stream_kernel(StreamParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -836,7 +867,7 @@ __global__ __launch_bounds__(OVF_NW * 64) void score_overflow_stream_kernel(Stre
     uint32_t* cbase = state_all + (size_t)wave * 2 * NB * SUB;
     uint32_t* cfill = cbase + NB * SUB;
     for (uint32_t b = lane; b < NB * SUB; b += 64) { cbase[b] = CHUNK_NONE; cfill[b] = CH; }
-    Appender<TBL, NB> app{p, cbase, cfill, 0u};
+    Appender<TBL, NB, LAYOUT> app{p, cbase, cfill, 0u};
     bool have_group = false;
     unsigned long long emitted = 0;
     constexpr uint32_t mulR = ipow(SIGMA, K - K / 2);
@@ -1158,7 +1189,11 @@ __device__ __forceinline__ uint2 pool_load(const uint2* p)
 #endif
 }
 
-template <uint32_t TBL, int NT, bool COMPRESS = false>
+// LAYOUT (ChunkLayout): PAIR6 chunks are read plane by plane, four consecutive pairs per lane and load -- a dwordx4 of scores and a
+// dwordx2 of their slots, half a load instruction per pair instead of one -- and the slot IS the table index.  A load is issued
+// where its first pair exists (index < n); the chunk's bytes behind n are allocated but hold nothing, and every pair is tested
+// against n again before it reaches the table.
+template <uint32_t TBL, int NT, bool COMPRESS = false, PairLayout LAYOUT = PairLayout::PAIR8>
 __global__ __launch_bounds__(NT) void reduce_buckets_kernel(const uint2* __restrict__ pool,
                                                            const uint64_t* __restrict__ off, const uint2* __restrict__ list,
                                                            uint32_t NB, uint64_t T, uint32_t* __restrict__ table,
@@ -1187,6 +1222,45 @@ __global__ __launch_bounds__(NT) void reduce_buckets_kernel(const uint2* __restr
     for (uint32_t i = threadIdx.x; i < CLR / 4; i += NT) reinterpret_cast<uint4*>(tab)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     const uint32_t k0 = (uint32_t)key0;
+    if constexpr (LAYOUT == PairLayout::PAIR6) {
+        using CL = ChunkLayout<TBL, LAYOUT>;
+        static_assert(CH % 256 == 0, "PAIR6 reduce: four pairs per lane and load");
+        static_assert(IPK_RB_NT == 0 && IPK_RB_ABL == 0, "the non-temporal and ablation knobs exist for the PAIR8 loads only: a tuning build must not measure PAIR6 by them");
+        constexpr int Q = CH / 256;                         // load pairs (scores x4, slots x4) per lane and chunk
+        const unsigned char* bytes = reinterpret_cast<const unsigned char*>(pool);
+        while (ci < c1) {
+            uint4 sc[CPT * Q]; uint2 sl[CPT * Q];
+            uint32_t n[CPT];
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                n[c] = (ci + (uint64_t)c * NWV < c1) ? e[c].y : 0u;
+                const unsigned char* s = bytes + (size_t)e[c].x * CL::BYTES;
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    const uint32_t q = lane + 64 * j;       // pairs 4 q .. 4 q + 3
+                    sc[c * Q + j] = make_uint4(0, 0, 0, 0); sl[c * Q + j] = make_uint2(0, 0);
+                    if (4 * q < n[c]) {
+                        sc[c * Q + j] = reinterpret_cast<const uint4*>(s)[q];
+                        sl[c * Q + j] = reinterpret_cast<const uint2*>(s + CL::SLOT_PLANE)[q];
+                    }
+                }
+            }
+            ci += (uint64_t)CPT * NWV;
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) if (ci + (uint64_t)c * NWV < c1) e[c] = list[ci + (uint64_t)c * NWV];
+#pragma unroll
+            for (int c = 0; c < CPT; ++c)
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    const uint32_t i0 = 4 * (lane + 64 * j);
+                    const uint4 s4 = sc[c * Q + j]; const uint2 k4 = sl[c * Q + j];
+                    if (i0 + 0 < n[c]) atomicMax(&tab[k4.x & (TBL - 1)], enc_score_bits(s4.x));
+                    if (i0 + 1 < n[c]) atomicMax(&tab[(k4.x >> 16) & (TBL - 1)], enc_score_bits(s4.y));
+                    if (i0 + 2 < n[c]) atomicMax(&tab[k4.y & (TBL - 1)], enc_score_bits(s4.z));
+                    if (i0 + 3 < n[c]) atomicMax(&tab[(k4.y >> 16) & (TBL - 1)], enc_score_bits(s4.w));
+                }
+        }
+    } else
     while (ci < c1) {
         constexpr int PER = CH / 64;                        // loads per lane and chunk
         uint2 v[CPT * PER];

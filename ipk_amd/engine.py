@@ -835,8 +835,8 @@ def _mem_stats(self, reset_peak=False):
 
 
 def _get_option(self, name):
-    """"workspace_bytes", "device_budget_bytes", "last_refused_bytes", "slice_long_lists" or "debug_sliced_windows" (the windows
-    scored in slices by this engine so far) (ipkgpu_get_option)."""
+    """"workspace_bytes", "device_budget_bytes", "last_refused_bytes", "slice_long_lists", "debug_sliced_windows" (the windows
+    scored in slices by this engine so far) or "debug_pool_bytes" (bytes the pair pool holds) (ipkgpu_get_option)."""
     _bind_keymajor(self._lib)
     v = C.c_int64(0)
     rc = self._lib.ipkgpu_get_option(self._h, name.encode(), C.byref(v))
