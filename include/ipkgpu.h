@@ -379,7 +379,7 @@ const uint32_t* ipkgpu_db_positions_device(const ipkgpu_db* d);
 double ipkgpu_db_time_ms(const ipkgpu_db* d);
 void ipkgpu_db_free(ipkgpu_db* d);
 
-/* ---- "next" row n1: MIF0 filter values and k-mer order (filter.cpp:55-119, db_builder.cpp:254-284) -- */
+/* ---- "next" row n1: filter values (MIF0, random) and k-mer order (filter.cpp:55-145, db_builder.cpp:254-284) -- */
 
 /* IPK's score threshold itself (un-vendored i2l::score_threshold; assumed powf(omega/sigma, k)). */
 float ipkgpu_score_threshold(float omega, uint32_t sigma, uint32_t k);
@@ -395,6 +395,15 @@ float ipkgpu_score_threshold(float omega, uint32_t sigma, uint32_t k);
  * only the last bit of the device's pow / log2 could differ from the host's libm.
  */
 int ipkgpu_db_filter_mif0(ipkgpu_ctx* ctx, ipkgpu_db* db, uint64_t total_num_groups, float threshold);
+/*
+ * The random filter (ipk.py build --filter random) over a database shard: filter value = a fixed draw in [0, 1) per k-mer CODE --
+ * the splitmix64 finaliser of the code, its top 24 bits times 2^-24 (exact in float) -- then the same order as above.
+ * This is THIS project's draw, not the reference's: random_filter (filter.cpp:122-145) draws uniform(0, 1) from
+ * std::default_random_engine(42) in the hash map's iteration order, which no other build reproduces.  One fixed draw per code
+ * means the file does not depend on sharding, key-range passes or on-disk batches.  Replaces the filter arrays the database
+ * has (as ipkgpu_db_filter_mif0 does); the accessors below and ipkgpu_db_write serve either filter.
+ */
+int ipkgpu_db_filter_random(ipkgpu_ctx* ctx, ipkgpu_db* db);
 /* host copies: filter value per k-mer (as the float i2l::kmer_fv stores, and in double), and the
  * positions of the k-mers in filter order: keys[order[0]] is written first */
 const float* ipkgpu_db_filter_values(ipkgpu_db* d);
@@ -475,7 +484,7 @@ typedef struct ipkgpu_db_header {
 
 /* save_header + save_phylo_kmer for every k-mer in filter order (db_builder.cpp:297-306,323-327), streamed from device
  * memory: the records are packed on the GPU in pieces, copied through pinned buffers and written while the next piece is
- * being packed.  Needs ipkgpu_db_filter_mif0 first.  Byte layout: ipk_amd/csrc/ipk_format.hpp -- i2l and Boost are
+ * being packed.  Needs ipkgpu_db_filter_mif0 or ipkgpu_db_filter_random first.  Byte layout: ipk_amd/csrc/ipk_format.hpp -- i2l and Boost are
  * un-vendored, so the layout is a reconstruction (Boost binary_oarchive primitives) and NOT pinned against a real .ipk.
  * A database that has positions (ipkgpu_db_positions_device != NULL) is written as the positioned file, byte for byte what
  * ipkgpu_db_write_host_positions writes from its host arrays; refused with that function's messages, before the file is created,

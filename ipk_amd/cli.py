@@ -6,7 +6,7 @@ ipk/src/command_line.cpp:83-147), and so does the flow of main.cpp:129-200 for t
   reference tree (-t) -> ghost nodes (extended_tree.cpp:76-162; saved as workdir/extended_trees/extended_tree.newick)
   -> AR outputs found by suffix in --ar-dir (ar.cpp:611-640: *.raxml.ancestralProbs, *.raxml.ancestralTree)
   -> AR tree rerooted if the reference tree is rooted (main.cpp:172-178) -> extended/AR node mapping (ar.cpp:790-834)
-  -> ghost groups (db_builder.cpp:495-553) -> GPU scoring -> MIF0 filter -> database file.
+  -> ghost groups (db_builder.cpp:495-553) -> GPU scoring -> filter (MIF0 or random, on the device) -> database file.
 
 Alignment reduction/extension and RUNNING the ancestral reconstruction are IPK's host stages and out of scope
 (DESIGN.md): their options are accepted for command-line compatibility and ignored; the AR outputs must exist (e.g. from
@@ -48,7 +48,9 @@ def ipk():
 @click.option("--no-reduction", is_flag=True, help="(ignored)")
 @click.option("--reduction-ratio", type=float, default=0.99, show_default=True, help="(ignored)")
 @click.option("--omega", type=float, default=1.5, show_default=True, help="score threshold (omega/#states)^k")
-@click.option("--filter", "filter_", type=click.Choice(["mif0", "random"]), default="mif0", show_default=True)
+@click.option("--filter", "filter_", type=click.Choice(["mif0", "random"]), default="mif0", show_default=True,
+              help="k-mer order of the file: mif0 (filter.cpp:55-119) or random -- this engine's fixed draw per k-mer code, not the "
+                   "reference's engine in hash-map order; both run on the device and feed the streamed device writer")
 @click.option("-u", "--mu", type=float, default=1.0, show_default=True, help="(parsed, unused -- as in the reference build)")
 @click.option("--ghosts", type=click.Choice(["inner-only", "outer-only", "both"]), default="both", show_default=True)
 @click.option("--use-unrooted", is_flag=True, help="(ignored)")
@@ -226,50 +228,25 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     t_score = time.time() - t0
     # MIF0's N = _original_tree.get_node_count() (db_builder.cpp:261); without a tree: groups = the non-root nodes (:524-553)
     n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
-    t0 = time.time()
     seq_name = "DNA" if sigma == 4 else "AA"
-    if filter_ == "mif0":
-        db.filter_mif0(eng, n_nodes, ipk_amd.score_threshold(omega, sigma, k))
-    t_filter = time.time() - t0
+    stage = {}
+
+    def write_shard(file):
+        # one filter stage and one writer for every filter, plain and --keep-positions (`db` then carries positions and the device
+        # writer packs the positioned records): the filter on the device, the records packed there in filter order and streamed
+        # to the file (ipkgpu_db_write) -- the database itself on one GPU, this rank's shard on several (a shard's header carries
+        # only its totals).  --filter random is this engine's draw, one fixed value per k-mer CODE (ipkgpu.h), not the reference's
+        # (filter.cpp:122-145), so the file does not depend on how the k-mers are sharded.
+        one = world == 1
+        stage["filter_s"], stage["write_s"] = dbfile.filter_and_write_device(
+            eng, db, file, filter_, seq_name, tree_index if one else [], newick if one else "", k, omega, n_nodes,
+            ipk_amd.score_threshold(omega, sigma, k))
     t0 = time.time()
-    if keep_positions and filter_ != "mif0":
-        # KEEP_POSITIONS (branch_group.cpp:73-86) with the random filter: the positioned database's host arrays (the position of every
-        # entry came out of the scoring pass with its score), the filter drawn as below
-        keys_db = db.keys()
-        br_db, sc_db = db.entries()
-        pos_db = db.positions()
-        fv_p = (dbfile.splitmix_unit(keys_db) if db.num_keys else np.zeros(0)).astype(np.float32)
-        order_p = np.argsort(dbfile.filter_sort_code(fv_p, keys_db), kind="stable")
-
-        def write_shard(file):
-            one = world == 1
-            dbfile.write_db_positions(file, seq_name, tree_index if one else [], newick if one else "", k, omega, keys_db, db.key_offsets(),
-                                      br_db, sc_db, pos_db, fv_p, order_p)
-    elif filter_ == "mif0":
-        # (--keep-positions: `db` carries positions, and the device writer packs the positioned records)
-        # records packed on the device in filter order and streamed to the file (ipkgpu_db_write): the database itself on one
-        # GPU, this rank's shard on several (a shard's header carries only its totals)
-        def write_shard(file):
-            if world == 1:
-                dbfile.write_db_device(eng, db, file, seq_name, tree_index, newick, k, omega)
-            else:
-                dbfile.write_db_device(eng, db, file, seq_name, [], "", k, omega)
-    else:
-        # random_filter (filter.cpp:122-145) draws uniform(0, 1) from std::default_random_engine(42) in the hash map's
-        # iteration order, which no other build reproduces; here: one fixed draw per k-mer CODE, so the file does not
-        # depend on how the k-mers are sharded
-        fv = (dbfile.splitmix_unit(db.keys()) if db.num_keys else np.zeros(0)).astype(np.float32)
-        order = np.argsort(dbfile.filter_sort_code(fv, db.keys()), kind="stable")
-        br, sc = db.entries()
-
-        def write_shard(file):
-            one = world == 1
-            dbfile.write_db(file, seq_name, tree_index if one else [], newick if one else "", k, omega, db.keys(), db.key_offsets(),
-                            br, sc, fv, order)
     totals = distributed.write_db_file(output, seq_name, tree_index, newick, k, omega, write_shard, workdir, dist, world, rank)
     if world == 1:
         totals = (db.num_keys, db.num_entries)
-    t_write = time.time() - t0
+    t_filter = stage["filter_s"]
+    t_write = time.time() - t0 - t_filter                            # the shard's write and, on several ranks, the merge of the shard files
     emitted = parts.emitted
     if world > 1:
         import torch

@@ -2748,31 +2748,24 @@ const uint32_t* ipkgpu_db_positions(ipkgpu_db* d)
 
 float ipkgpu_score_threshold(float omega, uint32_t sigma, uint32_t k) { return powf(omega / (float)sigma, (float)k); }
 
-int ipkgpu_db_filter_mif0(ipkgpu_ctx* ctx, ipkgpu_db* db, uint64_t total_num_groups, float threshold)
+// drops the filter arrays the database has and allocates new ones (both filter calls)
+static int db_filter_alloc(ipkgpu_ctx* ctx, ipkgpu_db* db)
 {
-    if (!ctx) return IPKGPU_ERR_INVALID;
-    if (!db || db->ctx != ctx) return fail(ctx, IPKGPU_ERR_INVALID, "database does not belong to this context");
-    if (total_num_groups == 0 || !(threshold > 0.0f)) return fail(ctx, IPKGPU_ERR_INVALID, "need total_num_groups > 0 and threshold > 0");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t n = db->n_keys;
     ctx_release(ctx, db->d_fv64); ctx_release(ctx, db->d_fv32); ctx_release(ctx, db->d_order);
     db->d_fv64 = nullptr; db->d_fv32 = nullptr; db->d_order = nullptr; db->h_filter_ok = false;
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv64, std::max<uint64_t>(n, 1) * 8));
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv32, std::max<uint64_t>(n, 1) * 4));
     HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_order, std::max<uint64_t>(n, 1) * 4));
-    if (n == 0) return IPKGPU_OK;
-    Stopwatch sw(ctx->stream, &ctx->events);
-    const int t0 = sw.mark();
-    for (uint64_t first = 0; first < n; first += WAVE_PER_ITEM_SPAN)
-        hipLaunchKernelGGL(mif0_kernel, dim3((uint32_t)((std::min<uint64_t>(WAVE_PER_ITEM_SPAN, n - first) + 3) / 4)), dim3(256), 0, ctx->stream,
-                           db->d_key_off, db->d_entries, n, (double)total_num_groups, (double)threshold, db->d_fv64, db->d_fv32, first);
-    HIP_TRY(ctx, hipGetLastError());
-    // order: ascending filter value (std::sort of kmer_order, db_builder.cpp:284), ties by ascending key
-    RC_TRY(ensure(ctx, ctx->tmp_a, n * 8));
-    RC_TRY(ensure(ctx, ctx->tmp_b, n * 8));
+    return IPKGPU_OK;
+}
+
+// what both filter calls do behind the sort keys in ctx->tmp_a (tmp_a, tmp_b: n * 8 bytes each): the sort, the order, the wait.
+// order: ascending filter value (std::sort of kmer_order, db_builder.cpp:284), ties by ascending key
+static int db_filter_sort_order(ipkgpu_ctx* ctx, ipkgpu_db* db, Stopwatch& sw, int t0)
+{
+    const uint64_t n = db->n_keys;
     const uint32_t nb = (uint32_t)((n + 255) / 256);
-    hipLaunchKernelGGL(filter_sortkey_kernel, dim3(nb), dim3(256), 0, ctx->stream, db->d_fv32, n, ctx->tmp_a.as<unsigned long long>());
-    HIP_TRY(ctx, hipGetLastError());
     size_t tmp_bytes = 0;
     HIP_TRY(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, ctx->tmp_a.as<unsigned long long>(), ctx->tmp_b.as<unsigned long long>(),
                                           (size_t)n, 0, 64, ctx->stream));
@@ -2785,6 +2778,48 @@ int ipkgpu_db_filter_mif0(ipkgpu_ctx* ctx, ipkgpu_db* db, uint64_t total_num_gro
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     db->t_filter = sw.ms(t0, t1);
     return IPKGPU_OK;
+}
+
+int ipkgpu_db_filter_mif0(ipkgpu_ctx* ctx, ipkgpu_db* db, uint64_t total_num_groups, float threshold)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (!db || db->ctx != ctx) return fail(ctx, IPKGPU_ERR_INVALID, "database does not belong to this context");
+    if (total_num_groups == 0 || !(threshold > 0.0f)) return fail(ctx, IPKGPU_ERR_INVALID, "need total_num_groups > 0 and threshold > 0");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_keys;
+    RC_TRY(db_filter_alloc(ctx, db));
+    if (n == 0) return IPKGPU_OK;
+    Stopwatch sw(ctx->stream, &ctx->events);
+    const int t0 = sw.mark();
+    for (uint64_t first = 0; first < n; first += WAVE_PER_ITEM_SPAN)
+        hipLaunchKernelGGL(mif0_kernel, dim3((uint32_t)((std::min<uint64_t>(WAVE_PER_ITEM_SPAN, n - first) + 3) / 4)), dim3(256), 0, ctx->stream,
+                           db->d_key_off, db->d_entries, n, (double)total_num_groups, (double)threshold, db->d_fv64, db->d_fv32, first);
+    HIP_TRY(ctx, hipGetLastError());
+    RC_TRY(ensure(ctx, ctx->tmp_a, n * 8));
+    RC_TRY(ensure(ctx, ctx->tmp_b, n * 8));
+    hipLaunchKernelGGL(filter_sortkey_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, db->d_fv32, n,
+                       ctx->tmp_a.as<unsigned long long>());
+    HIP_TRY(ctx, hipGetLastError());
+    return db_filter_sort_order(ctx, db, sw, t0);
+}
+
+int ipkgpu_db_filter_random(ipkgpu_ctx* ctx, ipkgpu_db* db)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (!db || db->ctx != ctx) return fail(ctx, IPKGPU_ERR_INVALID, "database does not belong to this context");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_keys;
+    RC_TRY(db_filter_alloc(ctx, db));
+    if (n == 0) return IPKGPU_OK;
+    Stopwatch sw(ctx->stream, &ctx->events);
+    const int t0 = sw.mark();
+    RC_TRY(ensure(ctx, ctx->tmp_a, n * 8));
+    RC_TRY(ensure(ctx, ctx->tmp_b, n * 8));
+    // value and sort key in one pass (filter_sortkey_kernel's key, fused)
+    hipLaunchKernelGGL(random_filter_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, db->d_keys, n, db->d_fv64,
+                       db->d_fv32, ctx->tmp_a.as<unsigned long long>());
+    HIP_TRY(ctx, hipGetLastError());
+    return db_filter_sort_order(ctx, db, sw, t0);
 }
 
 static bool db_filter_to_host(ipkgpu_db* d)
@@ -2937,7 +2972,7 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!db || db->ctx != ctx || !h || !path) return fail(ctx, IPKGPU_ERR_INVALID, "bad argument");
-    if (db->n_keys && (!db->d_fv32 || !db->d_order)) return fail(ctx, IPKGPU_ERR_INVALID, "filter values missing: call ipkgpu_db_filter_mif0 first");
+    if (db->n_keys && (!db->d_fv32 || !db->d_order)) return fail(ctx, IPKGPU_ERR_INVALID, "filter values missing: call ipkgpu_db_filter_mif0 or ipkgpu_db_filter_random first");
     if (db->n_keys >= 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many k-mers");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // a database with positions is written as the positioned file (ipkgpu_db_write_host_positions' layout and refusals, before the file exists)

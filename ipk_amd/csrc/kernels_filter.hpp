@@ -1,4 +1,4 @@
-// kernels_filter.hpp -- MIF0 filter values of a database shard.
+// kernels_filter.hpp -- filter values of a database shard: MIF0 and the random filter.
 //
 // Follows mif0_filter::calc_filter_values (ipk/src/filter.cpp:20-23,55-119), per k-mer, in double:
 //   s_i = (float) min(pow(10, log_score_i), 1.0)                         (logscore_to_score, :20-23)
@@ -73,6 +73,25 @@ __global__ __launch_bounds__(256) void filter_sortkey_kernel(const float* __rest
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     out[i] = ((unsigned long long)enc_score_bits(__float_as_uint(fv32[i])) << 32) | (unsigned long long)i;
+}
+// The random filter: one fixed draw in [0, 1) per k-mer CODE (dbfile.splitmix_unit: the splitmix64 finaliser of the code, its top
+// 24 bits), so the value does not depend on sharding, passes or batches.  24 bits fit a float's significand: fv32 is exact and
+// equals the double.  The sort key of filter_sortkey_kernel is written in the same pass.  One thread per k-mer.
+__global__ __launch_bounds__(256) void random_filter_kernel(const uint32_t* __restrict__ keys, uint64_t n,
+                                                            double* __restrict__ fv64, float* __restrict__ fv32,
+                                                            unsigned long long* __restrict__ sortkey)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    unsigned long long x = (unsigned long long)keys[i] + 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    const uint32_t v = (uint32_t)(x >> 40);
+    const float f = (float)v * 0x1p-24f;
+    fv32[i] = f;
+    fv64[i] = (double)f;
+    sortkey[i] = ((unsigned long long)enc_score_bits(__float_as_uint(f)) << 32) | (unsigned long long)i;
 }
 __global__ __launch_bounds__(256) void filter_order_kernel(const unsigned long long* __restrict__ sorted, uint64_t n,
                                                            uint32_t* __restrict__ order)

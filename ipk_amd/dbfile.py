@@ -3,8 +3,8 @@
 IPK streams its database through i2l::save_header / save_phylo_kmer over a Boost binary_oarchive
 (ipk/src/db_builder.cpp:145-146,176-177,297-306,323-327).  The byte layout lives in ONE place,
 ipk_amd/csrc/ipk_format.hpp (a reconstruction: i2l and Boost are un-vendored, so it is not pinned against a real .ipk);
-it is written by ipkgpu_db_write (streamed from the device) and ipkgpu_db_write_host (host arrays: merged shards).
-This module calls the latter and parses the layout back for the tests.
+it is written by ipkgpu_db_write (streamed from the device: every build path, filter_and_write_device) and ipkgpu_db_write_host
+(host arrays: the C ABI's host serialiser and the tests' yardstick).  This module calls both and parses the layout back for the tests.
 """
 import ctypes as C
 import struct
@@ -74,6 +74,23 @@ def write_db_device(engine, db, path, sequence_type, tree_index, newick, kmer_si
     if rc != 0:
         raise engine._err(rc)
     return int(n.value)
+
+
+def filter_and_write_device(engine, db, file, filter_, sequence_type, tree_index, newick, k, omega, n_nodes, threshold):
+    """The one filter-and-write stage of every build path: the shard `db` filtered on the device (filter_ "mif0": n_nodes = MIF0's N,
+    threshold = the score threshold, not its log; "random": neither is used) and streamed to `file` by the device writer.
+    Returns (seconds in the filter, seconds in the write)."""
+    import time
+    t0 = time.time()
+    if filter_ == "mif0":
+        db.filter_mif0(engine, n_nodes, threshold)
+    elif filter_ == "random":
+        db.filter_random(engine)
+    else:
+        raise ValueError(f"unknown filter {filter_!r} (mif0, random)")
+    t1 = time.time()
+    write_db_device(engine, db, file, sequence_type, tree_index, newick, k, omega)
+    return t1 - t0, time.time() - t1
 
 
 def write_times(engine):
@@ -220,7 +237,8 @@ def filter_sort_code(filter_values, keys):
 
 
 def splitmix_unit(keys):
-    """A reproducible value in [0, 1) per k-mer code (the `random` filter): independent of the sharding."""
+    """A reproducible value in [0, 1) per k-mer code (the `random` filter): independent of the sharding.  The host form of
+    random_filter_kernel (ipk_amd/csrc/kernels_filter.hpp), which the builds use (Db.filter_random)."""
     x = np.asarray(keys, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
     x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)

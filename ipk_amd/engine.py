@@ -395,6 +395,8 @@ def _bind_keymajor(L):
     L.ipkgpu_score_threshold.argtypes = [C.c_float, C.c_uint32, C.c_uint32]
     L.ipkgpu_db_filter_mif0.restype = C.c_int
     L.ipkgpu_db_filter_mif0.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float]
+    L.ipkgpu_db_filter_random.restype = C.c_int
+    L.ipkgpu_db_filter_random.argtypes = [C.c_void_p, C.c_void_p]
     L.ipkgpu_db_filter_values.restype = C.POINTER(C.c_float)
     L.ipkgpu_db_filter_values.argtypes = [C.c_void_p]
     L.ipkgpu_db_filter_values_f64.restype = C.POINTER(C.c_double)
@@ -436,6 +438,7 @@ ABI_SYMBOLS += [
     "ipkgpu_db_positions_device",
     "ipkgpu_score_groups_keymajor_positions_owners_device", "ipkgpu_merge_parts_positions_ptrs",
     "ipkgpu_parts_spill", "ipkgpu_spill_merge", "ipkgpu_mem_stats", "ipkgpu_get_option",
+    "ipkgpu_db_filter_random",
 ]
 
 
@@ -535,6 +538,12 @@ class Db:
     def filter_mif0(self, engine, total_num_groups, threshold):
         """MIF0 filter values + k-mer order (filter.cpp:55-119, db_builder.cpp:281-284) on the device."""
         rc = self._lib.ipkgpu_db_filter_mif0(engine._h, self._h, int(total_num_groups), C.c_float(threshold))
+        if rc != 0:
+            raise engine._err(rc)
+
+    def filter_random(self, engine):
+        """The random filter on the device: dbfile.splitmix_unit of every key as the filter value, and the k-mer order."""
+        rc = self._lib.ipkgpu_db_filter_random(engine._h, self._h)
         if rc != 0:
             raise engine._err(rc)
 

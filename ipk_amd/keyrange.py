@@ -67,29 +67,17 @@ def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, seq
         parts = engine.score_groups_keyrange(mats, mat_group, k, log_eps, lead, cls)
         db = engine.db_from_parts(parts, sigma, k)
         t1 = time.time()
-        if filter_ == "mif0":
-            db.filter_mif0(engine, n_nodes, thr)
-        else:
-            keys = db.keys()
-            fv = (dbfile.splitmix_unit(keys) if db.num_keys else np.zeros(0)).astype(np.float32)
-            order = np.argsort(dbfile.filter_sort_code(fv, keys), kind="stable")
-        t2 = time.time()
         file = os.path.join(pdir, f"pass{cls}.ipk")
-        if filter_ == "mif0":
-            dbfile.write_db_device(engine, db, file, sequence_type, [], "", k, omega)
-        else:
-            br, sc = db.entries()
-            dbfile.write_db(file, sequence_type, [], "", k, omega, keys, db.key_offsets(), br, sc, fv, order)
-        t3 = time.time()
+        filter_s, write_s = dbfile.filter_and_write_device(engine, db, file, filter_, sequence_type, [], "", k, omega, n_nodes, thr)
         paths.append(file)
         out["emitted"] += parts.emitted
         out["score_s"] += t1 - t0
-        out["filter_s"] += t2 - t1
-        out["write_s"] += t3 - t2
+        out["filter_s"] += filter_s
+        out["write_s"] += write_s
         out["per_pass"].append({"class": cls, "key_base": base, "keys": db.num_keys, "entries": db.num_entries,
                                 "emitted": parts.emitted, "call_ms": parts.time_ms(T_TOTAL), "score_ms": parts.time_ms(T_SCORE_MAIN),
                                 "reduce_ms": parts.time_ms(T_SCORE_REDUCE), "writer_ms": parts.time_ms(T_KM_WRITE),
-                                "keys_ms": db.time_ms(), "shard_file_s": t3 - t2})
+                                "keys_ms": db.time_ms(), "shard_file_s": write_s})
         db.free()
         parts.free()
     t0 = time.time()

@@ -229,18 +229,7 @@ def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, seq
             db = None
             try:
                 db = engine.spill_merge(sigma, k, b, B, blocks)
-                tf = time.time()
-                if filter_ == "mif0":
-                    db.filter_mif0(engine, n_nodes, thr)
-                    out["filter_s"] += time.time() - tf
-                    dbfile.write_db_device(engine, db, shard, sequence_type, [], "", k, omega)
-                else:
-                    keys = db.keys()
-                    fv = (dbfile.splitmix_unit(keys) if db.num_keys else np.zeros(0)).astype(np.float32)
-                    order_f = np.argsort(dbfile.filter_sort_code(fv, keys), kind="stable")
-                    out["filter_s"] += time.time() - tf
-                    br, sc = db.entries()
-                    dbfile.write_db(shard, sequence_type, [], "", k, omega, keys, db.key_offsets(), br, sc, fv, order_f)
+                out["filter_s"] += dbfile.filter_and_write_device(engine, db, shard, filter_, sequence_type, [], "", k, omega, n_nodes, thr)[0]
                 n_keys += db.num_keys
                 n_entries += db.num_entries
             except IpkGpuError as e:
