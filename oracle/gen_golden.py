@@ -1,9 +1,10 @@
 """Generates tests/golden/*.npz: seeded inputs + expected outputs of the hot path.
 
 The expected outputs come from oracle/ipk_oracle.c (the C restatement) and are asserted equal to
-oracle/np_oracle.py (the independent numpy restatement) before being written.  They are NOT outputs
-of the reference binary: the reference cannot be built here (see ipk_oracle.c header), so these are
-regression vectors of the oracle pair -- "parity unpinned".
+oracle/np_oracle.py (the independent numpy restatement) before being written, and to the reference's
+own compiled code (oracle/ref_build.py) where its binaries are present.  These files are regression
+vectors of the oracle pair; the vectors recorded from the reference itself are tests/golden/ref/
+(oracle/gen_ref_golden.py).  What of the oracle is pinned to the reference: see ipk_oracle.c header.
 
 Run from the repo root:  python -m oracle.gen_golden
 """
@@ -14,6 +15,7 @@ import numpy as np
 from ipk_amd.synth import synth_matrices
 from oracle import ipk_oracle as co
 from oracle import np_oracle as no
+from oracle import ref_build as rb
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
@@ -47,11 +49,18 @@ def main():
                 k2, s2, e2 = no.explore_group(grp, k, float(eps), bits)
                 assert np.array_equal(keys, k2) and np.array_equal(scores.view(np.uint32), s2.view(np.uint32))
                 assert emitted == e2
+            if rb.available():
+                k3, s3, e3 = rb.ref_explore_group(grp, k, float(eps), sigma)
+                assert np.array_equal(keys, k3) and np.array_equal(scores.view(np.uint32), s3.view(np.uint32)) and emitted == e3
             out[f"keys_{g}"] = keys
             out[f"score_bits_{g}"] = scores.view(np.uint32)
             out[f"emitted_{g}"] = np.uint64(emitted)
         # one window-level vector per case (window start 1 of matrix 0)
         wk, ws = co.window(mats[0], k, 1, float(eps))
+        if rb.available():
+            _, rk, rs = rb.ref_windows(mats[0], k, float(eps), sigma)[1]
+            o = np.argsort(rk, kind="stable")
+            assert np.array_equal(rk[o], wk) and np.array_equal(rs[o], ws.view(np.uint32))
         out["win_keys"] = wk
         out["win_score_bits"] = ws.view(np.uint32)
         path = os.path.join(OUT, name + ".npz")

@@ -1,0 +1,259 @@
+"""Generates tests/golden/ref/*.npz: inputs + the output of the REFERENCE'S OWN compiled code (oracle/ref_build.py).
+
+Unlike tests/golden/*.npz (oracle/gen_golden.py: regression vectors of the oracle), every expected value here was written by
+the binaries of oracle/_ref/: the reference's window.cpp + pk_compute.cpp per window, merged across windows and matrices by
+ref_build.merge_windows (the restatement of ipk::put), and the reference's filter.cpp for MIF0.  Before a file is written
+the generator asserts that oracle/ipk_oracle.c (explore_group and explore_group_pos) gives identical arrays, and
+oracle/np_oracle.py too where its dense enumeration reaches.
+
+Two input families:
+  synth   ipk_amd.synth.synth_matrices, as the parity tests use them, at small shapes
+  grid    every log-probability is -0.25 * an integer in 0..8 (some cases: about a tenth of the entries -inf) and eps is a
+          multiple of -0.25: every float sum is exact, so many candidates score exactly eps, many half-list entries sit exactly
+          on an inner bound eps - M(...), and equal scores across windows and matrices are common.  Where sigma^k allows, the
+          candidates scoring exactly eps and above it are counted by dense enumeration: both counts must reach 50, none of the
+          former may be in the reference's output, and the latter must be exactly what the reference emits.
+
+Run from the repo root, with the reference binaries built:  python -m oracle.gen_ref_golden
+"""
+import os
+import sys
+
+import numpy as np
+
+from ipk_amd.synth import synth_matrices
+from oracle import ipk_oracle as co
+from oracle import np_oracle as no
+from oracle import ref_build as rb
+
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ref")
+MAX_FILE = 180 * 1024            # no fixture larger than the largest one committed before (tests/golden/aa_k6.npz)
+MAX_DIR = 1 << 20
+DENSE_LIMIT = 2 * 10 ** 7        # sigma^k candidates a window that the generator enumerates
+NUMPY_LIMIT = 10 ** 6            # ... and that np_oracle (python loops over the survivors) is asked for
+
+SYNTH_GROUPS = np.array([5, 5, 9, 9], dtype=np.uint32)
+GRID_GROUPS = np.array([7, 3, 7, 3], dtype=np.uint32)      # interleaved, ids not ascending: groups come in first-seen order
+
+# name: (sigma, k, sites, alpha, omega, eps offset, seed)
+SYNTH = {
+    "synth_dna_k2": (4, 2, 12, 0.1, 1.5, 0.0, 202),
+    "synth_dna_k3": (4, 3, 12, 0.1, 1.5, 0.0, 203),
+    "synth_dna_k4": (4, 4, 12, 0.1, 1.5, 0.0, 204),
+    "synth_dna_k5": (4, 5, 12, 0.1, 1.5, 0.0, 205),
+    "synth_dna_k6": (4, 6, 14, 0.1, 1.5, 0.0, 206),
+    "synth_dna_k7": (4, 7, 14, 0.1, 1.5, 0.0, 207),
+    "synth_dna_k8": (4, 8, 16, 0.1, 1.5, 0.0, 208),
+    "synth_dna_k9": (4, 9, 16, 0.1, 1.5, 0.0, 209),
+    "synth_dna_k10": (4, 10, 14, 0.05, 1.5, 0.0, 210),
+    "synth_dna_k11": (4, 11, 15, 0.05, 1.5, 0.0, 211),
+    "synth_dna_k12": (4, 12, 16, 0.05, 1.5, 0.0, 212),
+    "synth_dna_k13": (4, 13, 17, 0.03, 1.5, 1.0, 1313),
+    "synth_dna_k14": (4, 14, 18, 0.05, 1.5, 1.5, 1314),
+    "synth_dna_k15": (4, 15, 19, 0.03, 1.5, 1.5, 1515),
+    "synth_dna_k16": (4, 16, 20, 0.05, 1.5, 2.5, 1516),
+    "synth_aa_k2": (20, 2, 10, 0.03, 1.5, 0.0, 302),
+    "synth_aa_k3": (20, 3, 10, 0.03, 1.5, 0.0, 303),
+    "synth_aa_k4": (20, 4, 10, 0.03, 1.5, 0.0, 304),
+    "synth_aa_k5": (20, 5, 9, 0.02, 1.5, 0.0, 305),
+    "synth_aa_k6": (20, 6, 10, 0.02, 1.5, 2.0, 306),
+}
+
+# name: (sigma, k, sites, eps, fraction of -inf entries, seed).  The uniform grid makes the best score of a window vary a lot from
+# matrix to matrix, so eps (and for some cases the seed) was searched for the first value at which both groups emit at least 60
+# k-mers, the case emits at most 3000, and -- within the dense enumeration's reach -- 50 candidates lie on eps and 50 above it.
+GRID = {
+    "grid_dna_k2": (4, 2, 16, -1.25, 0.0, 2),
+    "grid_dna_k3": (4, 3, 16, -1.5, 0.1, 3),
+    "grid_dna_k4": (4, 4, 16, -2.25, 0.0, 4),
+    "grid_dna_k5": (4, 5, 16, -1.75, 0.1, 5),
+    "grid_dna_k6": (4, 6, 16, -2.25, 0.0, 6),
+    "grid_dna_k7": (4, 7, 16, -3.5, 0.1, 7),
+    "grid_dna_k8": (4, 8, 16, -2.5, 0.0, 8),
+    "grid_dna_k9": (4, 9, 16, -3.75, 0.1, 109),
+    "grid_dna_k10": (4, 10, 18, -4.0, 0.0, 110),
+    "grid_dna_k11": (4, 11, 18, -4.0, 0.1, 111),
+    "grid_dna_k12": (4, 12, 18, -5.5, 0.0, 12),
+    "grid_dna_k13": (4, 13, 20, -4.25, 0.1, 213),
+    "grid_dna_k14": (4, 14, 20, -4.25, 0.0, 14),
+    "grid_dna_k15": (4, 15, 22, -5.25, 0.1, 15),
+    "grid_dna_k16": (4, 16, 22, -5.0, 0.0, 416),
+    "grid_aa_k2": (20, 2, 8, -0.5, 0.0, 22),
+    "grid_aa_k3": (20, 3, 8, -0.25, 0.1, 23),
+    "grid_aa_k4": (20, 4, 8, -0.5, 0.0, 124),
+    "grid_aa_k5": (20, 5, 8, -0.5, 0.1, 25),
+    "grid_aa_k6": (20, 6, 8, -0.5, 0.0, 26),
+}
+
+MIF0_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 200)
+
+
+def grid_matrices(n_mats, sites, sigma, seed, ninf_fraction=0.0, rng=None):
+    """float32 [n_mats, sites, sigma]: every entry -0.25 * an integer in 0..8 (+0.0, never -0.0), a fraction of them -inf.
+    Matrix n_mats // 2 + i repeats matrix i one site further down (its first site stays its own): with GRID_GROUPS the two
+    matrices of a group then score the same k-mers alike in windows one position apart, so the max-merge meets equal scores
+    at every key they share and the first window has to keep its position."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    m = (np.float32(-0.25) * rng.integers(0, 9, size=(n_mats, sites, sigma)).astype(np.float32)) + np.float32(0.0)
+    if ninf_fraction > 0:
+        m[rng.random(size=m.shape) < ninf_fraction] = -np.inf
+    half = n_mats // 2
+    for i in range(half):
+        m[half + i, 1:] = m[i, :-1]
+    return np.ascontiguousarray(m, dtype=np.float32)
+
+
+def tenth_matrices(n_mats, sites, sigma, seed, rng=None):
+    """float32 [n_mats, sites, sigma]: every entry float32(-0.1) * an integer in 0..8.  A tenth is no binary fraction: candidates
+    that tie as real numbers differ in the last bits as float sums, and the prefix sums behind M(...) carry rounding, so the
+    hierarchical bounds eps - M(...) -- not only the final a + b > eps -- decide k-mers at the threshold."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    m = (np.float32(-0.1) * rng.integers(0, 9, size=(n_mats, sites, sigma)).astype(np.float32)) + np.float32(0.0)
+    return np.ascontiguousarray(m, dtype=np.float32)
+
+
+def dense_window_scores(m, k, start):
+    """All sigma^k candidate scores of one window, indexed by key rank (first symbol most significant).  On grid inputs every
+    sum is exact, so the association of the additions does not matter."""
+    s = m[start].astype(np.float32)
+    for j in range(1, k):
+        s = (s[:, None] + m[start + j][None, :]).reshape(-1)
+    return s
+
+
+def dense_key(rank, k, sigma, bits):
+    """The packed key of the candidate with the given rank among the sigma^k (rank = sum of symbol * sigma^(k-1-j))."""
+    rank = np.asarray(rank, dtype=np.uint64)
+    key = np.zeros(rank.shape, dtype=np.uint64)
+    for j in range(k):
+        sym = (rank // np.uint64(sigma ** (k - 1 - j))) % np.uint64(sigma)
+        key |= sym << np.uint64(bits * (k - 1 - j))
+    return key.astype(np.uint32)
+
+
+def count_on_and_above(mats, per_matrix, k, eps, sigma):
+    """Dense count of the (window, k-mer) candidates scoring exactly eps and above it; asserts that the reference's output of
+    every window is exactly the candidates above eps (so none of those on eps), with the dense sum's bits."""
+    bits = co.bits(sigma)
+    eps = np.float32(eps)
+    on = above = 0
+    for m, wins in zip(mats, per_matrix):
+        for pos, keys, sbits in wins:
+            s = dense_window_scores(m, k, pos)
+            on_rank = np.flatnonzero(s == eps)
+            ab_rank = np.flatnonzero(s > eps)
+            on += len(on_rank)
+            above += len(ab_rank)
+            assert not np.isin(dense_key(on_rank, k, sigma, bits), keys).any(), "a candidate scoring exactly eps was emitted"
+            want = dense_key(ab_rank, k, sigma, bits)
+            o, w = np.argsort(keys, kind="stable"), np.argsort(want, kind="stable")
+            assert np.array_equal(keys[o], want[w]), "the reference's window is not the dense set above eps"
+            assert np.array_equal(sbits[o], s[ab_rank][w].view(np.uint32)), "score bits differ from the dense sums"
+    return on, above
+
+
+def tying_window_pairs(per_matrix_of_group, keys, scores):
+    """How many keys of a group have their kept score reached by two or more windows (ties the max-merge has to break)."""
+    allk = np.concatenate([w[1] for wins in per_matrix_of_group for w in wins])
+    alls = np.concatenate([w[2] for wins in per_matrix_of_group for w in wins]).view(np.float32)
+    kept = scores[np.searchsorted(keys, allk)]
+    hit = allk[alls == kept]
+    _, cnt = np.unique(hit, return_counts=True)
+    return int((cnt >= 2).sum())
+
+
+def record_case(name, family, mats, mat_group, k, eps, sigma):
+    """Runs the reference, checks the oracles against it and returns the fixture's arrays."""
+    eps = float(np.float32(eps))
+    per_matrix = rb.ref_windows_many(mats, k, eps, sigma)
+    order = list(dict.fromkeys(mat_group.tolist()))
+    out = {"logp": mats, "sigma": np.uint32(sigma), "k": np.uint32(k), "eps_bits": np.array(eps, np.float32).view(np.uint32),
+           "mat_group": mat_group, "family": np.array(family), "group_ids": np.array(order, dtype=np.uint32)}
+    ties = 0
+    for gi, gid in enumerate(order):
+        sel = np.flatnonzero(mat_group == gid)
+        wins = [per_matrix[i] for i in sel]
+        keys, scores, pos, emitted = rb.merge_windows(wins, positions=True)
+        ok, os_, oe = co.explore_group(mats[sel], k, eps)
+        assert np.array_equal(ok, keys) and np.array_equal(os_.view(np.uint32), scores.view(np.uint32)) and oe == emitted, name
+        pk, ps, pp, pe = co.explore_group_pos(mats[sel], k, eps)
+        assert np.array_equal(pk, keys) and np.array_equal(ps.view(np.uint32), scores.view(np.uint32)), name
+        assert np.array_equal(pp, pos) and pe == emitted, name
+        if sigma ** k <= NUMPY_LIMIT:
+            nk, ns, ne = no.explore_group(mats[sel], k, eps, co.bits(sigma))
+            assert np.array_equal(nk, keys) and np.array_equal(ns.view(np.uint32), scores.view(np.uint32)) and ne == emitted, name
+            _, _, npos = no.explore_group_pos(mats[sel], k, eps, co.bits(sigma))
+            assert np.array_equal(npos, pos), name
+        assert len(keys) > 0, f"{name}: group {gid} is empty"
+        ties += tying_window_pairs(wins, keys, scores)
+        out[f"keys_{gi}"] = keys
+        out[f"score_bits_{gi}"] = scores.view(np.uint32)
+        out[f"positions_{gi}"] = pos
+        out[f"emitted_{gi}"] = np.uint64(emitted)
+    on = above = -1
+    if family == "grid":
+        if sigma ** k <= DENSE_LIMIT:
+            on, above = count_on_and_above(mats, per_matrix, k, eps, sigma)
+            assert on >= 50 and above >= 50, f"{name}: {on} candidates on eps, {above} above: choose another threshold"
+        assert ties >= 1, f"{name}: no two windows tie on a key's kept score"
+    out["on_eps"], out["above_eps"], out["tied_keys"] = np.int64(on), np.int64(above), np.int64(ties)
+    return out
+
+
+def mif0_case():
+    """Entry lists of the lengths around the kernel's 64-entry chunks, each with N == n and N > n."""
+    rng = np.random.default_rng(64)
+    thr = np.float32(co.score_threshold(1.5, 4, 8))
+    log_thr = co.log10f(np.array([thr], np.float32))[0]
+    lists, Ns = [], []
+    for n in MIF0_LENGTHS:
+        for N in (n, n + 37):
+            s = (np.float32(log_thr) * rng.random(n).astype(np.float32)).astype(np.float32)     # (log_thr, 0]
+            s[0] = np.float32(0.0)                                             # a probability of exactly 1
+            if n >= 2:
+                s[n - 1] = np.nextafter(log_thr, np.float32(0.0))              # just above the log threshold
+            if n >= 63:
+                s[n // 2] = np.float32(0.3)                                    # a positive log score: clamped to 1
+            lists.append(s)
+            Ns.append(N)
+    fv = np.array([rb.ref_mif0([s], N, thr)[0] for s, N in zip(lists, Ns)], dtype=np.float64)
+    for s, N, v in zip(lists, Ns, fv):
+        assert np.float64(co.mif0(s, N, thr)).view(np.uint64) == v.view(np.uint64), (len(s), N)
+    return {"scores": np.concatenate(lists), "offsets": np.cumsum([0] + [len(s) for s in lists]).astype(np.int64),
+            "N": np.array(Ns, dtype=np.int64), "threshold_bits": np.array(thr, np.float32).view(np.uint32), "fv_bits": fv.view(np.uint64)}
+
+
+def main():
+    if not rb.available():
+        sys.exit("the reference binaries are not in oracle/_ref/: run oracle.ref_build.build() where the reference tree is")
+    os.makedirs(OUT, exist_ok=True)
+    total = 0
+
+    def write(name, arrays):
+        nonlocal total
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, **arrays)
+        size = os.path.getsize(path)
+        assert size <= MAX_FILE, f"{name}: {size} bytes"
+        total += size
+        return size
+
+    for name, (sigma, k, sites, alpha, omega, offset, seed) in SYNTH.items():
+        mats = synth_matrices(4, sites, sigma, alpha, seed)
+        eps = np.float32(co.log_threshold(omega, sigma, k) + offset)
+        out = record_case(name, "synth", mats, SYNTH_GROUPS, k, eps, sigma)
+        print(f"{name}: {write(name, out)} bytes, entries {[len(out[f'keys_{g}']) for g in range(2)]}, "
+              f"emitted {[int(out[f'emitted_{g}']) for g in range(2)]}, tied keys {int(out['tied_keys'])}")
+    for name, (sigma, k, sites, eps, ninf, seed) in GRID.items():
+        mats = grid_matrices(4, sites, sigma, seed, ninf)
+        out = record_case(name, "grid", mats, GRID_GROUPS, k, eps, sigma)
+        print(f"{name}: {write(name, out)} bytes, entries {[len(out[f'keys_{g}']) for g in range(2)]}, "
+              f"emitted {[int(out[f'emitted_{g}']) for g in range(2)]}, on eps {int(out['on_eps'])}, above {int(out['above_eps'])}, "
+              f"tied keys {int(out['tied_keys'])}")
+    print(f"mif0: {write('mif0', mif0_case())} bytes")
+    assert total <= MAX_DIR, total
+    print("total", total, "bytes")
+
+
+if __name__ == "__main__":
+    main()

@@ -4,12 +4,16 @@
  * THIS IS TEST INFRASTRUCTURE, NOT PRODUCT CODE.  Only tests/, __graft_entry__.smoke()
  * and bench.py's cpu_baseline leg may load it.  The product path (ipk_amd/) never calls it.
  *
- * PARITY UNPINNED: the reference's hot-path translation units need the un-vendored i2l
- * headers (empty submodule) so they cannot be compiled here without stand-in headers, and
- * the reference's only goldens (tests/data/D652, D140) are git-LFS pointer stubs.  This file
- * therefore restates the algorithm from the reference *source text*; it is cross-checked
- * against an independently written numpy restatement (oracle/np_oracle.py), not against
- * outputs of the reference itself.
+ * PARITY: this file restates the algorithm from the reference's source text, and is pinned to the
+ * reference's own compiled code where that can be built -- oracle/ref_build.py compiles window.cpp,
+ * pk_compute.cpp and filter.cpp unchanged against the stand-in i2l headers of oracle/ref_shim/;
+ * tests/golden/ref/ holds their recorded output and tests/test_ref_pin.py compares, bit for bit:
+ *   pinned        matrix::preprocess, the window iteration, DCLA::DC (with as_column),
+ *                 mif0_filter::calc_filter_values (as the double it computes)
+ *   source text   the i2l constants (bits per symbol, key and score types),
+ *   or SURVEY.md  score_threshold (i2l), ipk::put (branch_group.cpp is not compiled: boost
+ *                 serialisation), the narrowing of the filter value to float (i2l)
+ * It is also cross-checked against an independently written numpy restatement (oracle/np_oracle.py).
  *
  * Each function cites the reference lines (relative to /root/reference) it follows.
  * All score arithmetic is IEEE binary32, one operation per rounding (compile with

@@ -1,7 +1,7 @@
 """ctypes front-end of oracle/libipk_oracle.so (the C restatement, oracle/ipk_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg.  PARITY UNPINNED (see the header of ipk_oracle.c).
+cpu_baseline leg.  Pinned to the compiled reference on the scoring hot path and MIF0 (see the header of ipk_oracle.c).
 """
 import ctypes as C
 import os

@@ -4,7 +4,7 @@ Written as a *set definition* (dense enumeration of all sigma^h candidates per t
 boolean survivor masks), deliberately unlike the list/sort/early-break structure of
 oracle/ipk_oracle.c (which follows ipk/src/pk_compute.cpp:42-114 statement by statement), so that
 agreement between the two is evidence neither mis-states the reference.  Small k only
-(sigma^k candidates are materialised).  PARITY UNPINNED: see ipk_oracle.c.
+(sigma^k candidates are materialised).  What is pinned to the compiled reference: see ipk_oracle.c.
 """
 import numpy as np
 
