@@ -404,6 +404,52 @@ __device__ __forceinline__ void store_pair_if_gt(unsigned long long& cursor, uin
                  : "+v"(cursor) : "v"(data), "v"(s), "s"(eps) : "vcc");
 }
 
+// The half joins of the candidate-per-lane kernels (k = 8..10) for a window that left the single-step form because ONE of its
+// halves has more than 64 candidates (16.7 % of cfg2's windows; in nearly all of them the other half has <= 64).  Same float
+// operations, codes and list order as join_to_list (pk_compute.cpp:90-91; first child ascending, then second child ascending).
+//
+// A half with <= 64 candidates: the single-step form, for one half.
+template <uint32_t MUL>
+__device__ __forceinline__ uint32_t half_join_single(const uint2* A, const uint2* B, uint32_t nb, uint32_t total, float eps, uint2* out,
+                                                     uint32_t lane, float lane_h)
+{
+    const float rn = __builtin_amdgcn_rcpf((float)nb);                               // (1 ulp: ample for div_small)
+    const uint32_t i = div_small(lane_h, rn), j = (uint32_t)(__mul24((int)i, -(int)nb) + (int)lane);
+    const uint2 a = A[i], b = B[j];                                                  // lanes past the candidates read on in LDS: masked below
+    const float s = __uint_as_float(a.y) + __uint_as_float(b.y);                     // :90
+    const bool v = lane < total, c = s > eps;                                        // :91
+    const uint64_t h = ballot64(v) & ballot64(c);
+    if (v && c) out[mbcnt(h)] = make_uint2(a.x * MUL + b.x, __float_as_uint(s));
+    return (uint32_t)__popcll(h);
+}
+// A half with > 64 candidates: the final join's scheme.  The second child's list (nb <= 64 entries) sits in registers, one entry
+// per lane, floor(64 / nb) rows of the first child per step; the lane roles are fixed once per half, so a step is one LDS read,
+// add, compare, ballot, rank and write -- no division and no fix-up per step (for_each_pair's flattened walk divides every step).
+// More than `cap` survivors: LIST_OVERFLOW, and nothing past out[cap) is written (exactly `cap` is no overflow).
+template <uint32_t MUL>
+__device__ __forceinline__ uint32_t half_join_rows(const uint2* A, uint32_t na, const uint2* B, uint32_t nb, float eps, uint2* out, uint32_t cap,
+                                                   uint32_t lane, float lane_h)
+{
+    const float rn = __builtin_amdgcn_rcpf((float)nb);
+    const uint32_t rps = to_sgpr(div_small(64.5f, rn));                              // rows per step
+    const uint32_t rsel = div_small(lane_h, rn), col = lane - __umul24(rsel, nb);
+    const uint2 b = B[col];
+    const float by = __uint_as_float(b.y);
+    const uint2* ap = A + rsel;                                                      // rows past na read on in LDS: masked below
+    uint32_t n = 0;
+    for (uint32_t i0 = 0; i0 < na; i0 += rps) {
+        const uint2 a = ap[i0];
+        const float s = __uint_as_float(a.y) + by;                                   // :90
+        const bool live = lane < min(rps, na - i0) * nb, c = s > eps;                // :91  (whole rows only)
+        const uint64_t m = ballot64(live) & ballot64(c);
+        const uint32_t cnt = (uint32_t)__popcll(m);
+        if (n + cnt > cap) return LIST_OVERFLOW;
+        if (live && c) (out + n)[mbcnt(m)] = make_uint2(a.x * MUL + b.x, __float_as_uint(s));   // (out + n: scalar)
+        n += cnt;
+    }
+    return n;
+}
+
 // COUNT_ONLY: the pool-sizing pre-pass of a context's first call -- same windows, same lists, the final join only counts its
 // survivors (nothing is reserved or stored); a separate instantiation so that it shows under its own name in a kernel trace.
 //
@@ -615,12 +661,21 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
                 } else {
                     // (the list lengths are wave-uniform by construction; without the readfirstlane the branches below count as
                     //  divergent, and every value carried around this loop -- the appender's state -- is then held in VGPRs)
+                    if constexpr (!ROWLANE) {
+                        // each half by its own size (half_join_single / half_join_rows above); an empty L: R is not built
+                        nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tl <= 64 ? half_join_single<Q::FLB * mulR>(la, lb, nlb, tl, eps_l, lp, lane, lane_h)
+                                                                                       : half_join_rows<Q::FLB * mulR>(la, nla, lb, nlb, eps_l, lp, CAPL, lane, lane_h)));
+                        nR = nL == LIST_OVERFLOW || nL == 0 ? nL
+                           : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tr <= 64 ? half_join_single<Q::FRB>(ra, rb, nrb, tr, eps_r, rp, lane, lane_h)
+                                                                                      : half_join_rows<Q::FRB>(ra, nra, rb, nrb, eps_r, rp, CAPR, lane, lane_h)));
+                    } else {
                     if (!keep_l)
                         nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)join_to_list(la + ia, min(sla, nla - ia), lb, nlb, eps_l, Q::FLB * mulR, lp, CAPL));
                     if constexpr (SLICE) {
                         if (nL == LIST_OVERFLOW) { sla = SAFE_L; continue; }            // (only a whole list overflows: ia == 0)
                     }
                     nR = nL == LIST_OVERFLOW || nL == 0 ? nL : (uint32_t)__builtin_amdgcn_readfirstlane((int)join_to_list(ra + ir, min(sra, nra - ir), rb, nrb, eps_r, Q::FRB, rp, CAPR));
+                    }
                     if constexpr (SLICE) {
                         if (nR == LIST_OVERFLOW) { sra = SAFE_R; keep_l = true; continue; }   // (ir == 0; L's slice stays as it is)
                     } else if (nL == LIST_OVERFLOW || nR == LIST_OVERFLOW) {
