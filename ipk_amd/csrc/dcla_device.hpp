@@ -76,13 +76,18 @@ __device__ unsigned int g_exec_violations;
 // One 8-byte record per lane of `mask` to uniform_base + byte_off (+ IMM bytes): the store form with a scalar base and a 32-bit
 // lane offset, the lanes selected by writing exec directly -- from code that runs with ALL lanes enabled (uniform control flow
 // in full wavefronts).  Two scalar instructions around the store instead of compare / and-saveexec / branch / restore.
-template <int IMM = 0>
+// NTS: a non-temporal store (`nt`), for data that nothing reads again before it has left the caches.
+template <int IMM = 0, bool NTS = false>
 __device__ __forceinline__ void store8_lanes(const void* uniform_base, uint32_t byte_off, uint32_t x, uint32_t y, uint64_t mask)
 {
     u32x2_t data; data.x = x; data.y = y;
     IPK_ASSERT_FULL_EXEC();
-    asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx2 %0, %1, %2 offset:%4\n\ts_mov_b64 exec, -1"
-                 : : "v"(byte_off), "v"(data), "s"(uniform_base), "s"(mask), "n"(IMM) : "memory");
+    if constexpr (NTS)
+        asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx2 %0, %1, %2 offset:%4 nt\n\ts_mov_b64 exec, -1"
+                     : : "v"(byte_off), "v"(data), "s"(uniform_base), "s"(mask), "n"(IMM) : "memory");
+    else
+        asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx2 %0, %1, %2 offset:%4\n\ts_mov_b64 exec, -1"
+                     : : "v"(byte_off), "v"(data), "s"(uniform_base), "s"(mask), "n"(IMM) : "memory");
 }
 // the 4-byte form (the sequence numbers that travel beside the pairs of a positioned call)
 template <int IMM = 0>

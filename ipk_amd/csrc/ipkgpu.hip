@@ -2227,7 +2227,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
             hipLaunchKernelGGL(km_count_mask_kernel, dim3((uint32_t)(((T + 31) / 32 + 255) / 256)), dim3(256), 0, ctx->stream,
                                ctx->mask.as<uint32_t>(), ctx->mask_words, T, gb, P, slots, b.counts, qpack);
         else if (ctx->mask_valid)
-            hipLaunchKernelGGL(km_count_mask_key_kernel, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, ctx->stream,
+            hipLaunchKernelGGL(km_count_mask_slice_kernel, dim3((uint32_t)(((T + 31) / 32 + KMS_WORDS - 1) / KMS_WORDS)), dim3(KMS_WORDS * KMS_SLICES), 0, ctx->stream,
                                ctx->mask.as<uint32_t>(), ctx->mask_words, T, gb, P, slots, b.counts, qpack);
         else
             hipLaunchKernelGGL(km_count_kernel, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -2304,7 +2304,7 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
                             hipLaunchKernelGGL(km_count_mask_kernel, dim3((uint32_t)(((T + 31) / 32 + 255) / 256)), dim3(256), 0, ctx->stream,
                                                pmask, ctx->mask_words, T, pg, P, slots, ctx->pcounts.as<uint32_t>(), ctx->qpack.as<uint32_t>());
                         else
-                            hipLaunchKernelGGL(km_count_mask_key_kernel, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, ctx->stream,
+                            hipLaunchKernelGGL(km_count_mask_slice_kernel, dim3((uint32_t)(((T + 31) / 32 + KMS_WORDS - 1) / KMS_WORDS)), dim3(KMS_WORDS * KMS_SLICES), 0, ctx->stream,
                                                pmask, ctx->mask_words, T, pg, P, slots, ctx->pcounts.as<uint32_t>(), ctx->qpack.as<uint32_t>());
                         HIP_TRY(ctx, hipGetLastError());
                         CompTable ctp = comp_table_w();
@@ -2331,10 +2331,13 @@ int keymajor_impl(ipkgpu_ctx* ctx, const float* logp_dev, uint32_t n_mats, uint3
                 hipLaunchKernelGGL(km_write_kernel, dim3((uint32_t)((T + 63) / 64)), dim3(256), 0, ctx->stream,
                                    ctx->table.as<uint32_t>(), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots,
                                    ctx->offsets.as<uint64_t>(), b.entries, cap_e);
-            else
-                hipLaunchKernelGGL(km_write_lines_kernel, dim3((uint32_t)((T + 63) / 64)), dim3(256), 0, ctx->stream,
+            else {
+                // (non-temporal entry stores; debug_flags bit 14: the plain stores they replaced, for the comparison)
+                const auto lines = (ctx->opt_flags & 16384) ? km_write_lines_kernel<false> : km_write_lines_kernel<true>;
+                hipLaunchKernelGGL(lines, dim3((uint32_t)((T + 63) / 64)), dim3(256), 0, ctx->stream,
                                    ctx->table.as<uint32_t>(), T, gb, ctx->branch.as<uint32_t>() + g0, P, slots,
                                    ctx->offsets.as<uint64_t>(), b.entries, cap_e);
+            }
             HIP_TRY(ctx, hipGetLastError());
             return IPKGPU_OK;
         };

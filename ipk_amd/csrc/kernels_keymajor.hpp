@@ -111,34 +111,69 @@ __global__ __launch_bounds__(256) void km_count_mask_kernel(const uint32_t* __re
     }
 }
 
-// One thread per key: for key spaces too small to fill the chip with one thread per mask word (DNA k <= 11).
-__global__ __launch_bounds__(256) void km_count_mask_key_kernel(const uint32_t* __restrict__ mask, uint64_t W, uint64_t T,
-                                                                uint32_t G, uint32_t P, uint64_t slots, uint32_t* __restrict__ counts,
-                                                                uint32_t* __restrict__ qpack)
+// For key spaces too small to fill the chip with one thread per mask word (DNA k <= 11): a thread per (mask word, slice of the
+// groups), 32 words x 16 slices per workgroup, so every mask word is loaded once (a thread per key loaded it 32 times) and 4^10 keys
+// still make 2048 threads per CU.  The slices are the four quarters of ceil(G / 4) rows that qpack counts by (km_count_mask_kernel),
+// each cut in four; a slice counts in bit planes like km_count_mask_kernel and adds its 32 counts to the workgroup's totals in LDS.
+constexpr uint32_t KMS_WORDS = 32, KMS_SLICES = 16;
+__global__ __launch_bounds__(KMS_WORDS * KMS_SLICES) void km_count_mask_slice_kernel(const uint32_t* __restrict__ mask, uint64_t W, uint64_t T,
+                                                                  uint32_t G, uint32_t P, uint64_t slots, uint32_t* __restrict__ counts,
+                                                                  uint32_t* __restrict__ qpack)
 {
-    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (x >= T) return;
-    const uint32_t* m = mask + (x >> 5);
-    const uint32_t sh = (uint32_t)x & 31u;
-    const uint32_t step = qpack ? (G + 3) / 4 : G;          // (per-quarter counts: see km_count_mask_kernel)
-    uint32_t total = 0, pack = 0, q = 0;
-    for (uint32_t g0 = 0; g0 < G; g0 += step, ++q) {
-        const uint32_t g1 = min(G, g0 + step);
-        uint32_t c = 0, g = g0;
-        for (; g + 16 <= g1; g += 16) {                     // sixteen rows' loads in flight together
-            uint32_t v[16];
+    constexpr uint32_t NT = KMS_WORDS * KMS_SLICES, NK = KMS_WORDS * 32;
+    __shared__ uint32_t tot[32 * (KMS_WORDS + 1)], pk[32 * (KMS_WORDS + 1)];      // [bit][word], padded: both sides free of bank conflicts
+    for (uint32_t i = threadIdx.x; i < 32 * (KMS_WORDS + 1); i += NT) { tot[i] = 0; pk[i] = 0; }
+    __syncthreads();
+    const uint32_t wl = threadIdx.x % KMS_WORDS, s = threadIdx.x / KMS_WORDS;
+    const uint64_t w = (uint64_t)blockIdx.x * KMS_WORDS + wl;
+    const uint32_t step = (G + 3) / 4, q = s >> 2;
+    const uint32_t q0 = min(G, q * step), q1 = min(G, q0 + step);               // the quarter (empty where G < 4 leaves none)
+    const uint32_t sub = (q1 - q0 + 3) / 4;
+    const uint32_t s0 = min(q1, q0 + (s & 3u) * sub), s1 = min(q1, s0 + sub);   // this thread's rows
+    if (w * 32 < T) {
+        const uint32_t* m = mask + w;
+        for (uint32_t g0 = s0; g0 < s1; g0 += 255) {                            // (8 bit planes hold 255 rows)
+            const uint32_t g1 = min(s1, g0 + 255u);
+            uint32_t plane[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            uint32_t g = g0;
+            for (; g + 8 <= g1; g += 8) {                  // eight rows' loads in flight together
+                uint32_t v[8];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = m[(size_t)(g + u) * W];
+                for (int u = 0; u < 8; ++u) v[u] = m[(size_t)(g + u) * W];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) c += (v[u] >> sh) & 1u;
+                for (int u = 0; u < 8; ++u) {
+                    uint32_t carry = v[u];
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) { const uint32_t t = plane[p] & carry; plane[p] ^= carry; carry = t; }
+                }
+            }
+            for (; g < g1; ++g) {
+                uint32_t carry = m[(size_t)g * W];
+#pragma unroll
+                for (int p = 0; p < 8; ++p) { const uint32_t t = plane[p] & carry; plane[p] ^= carry; carry = t; }
+            }
+#pragma unroll
+            for (int b = 0; b < 32; ++b) {
+                uint32_t c = 0;
+#pragma unroll
+                for (int p = 0; p < 8; ++p) c |= ((plane[p] >> b) & 1u) << p;
+                if (c) {
+                    atomicAdd(&tot[b * (KMS_WORDS + 1) + wl], c);
+                    if (qpack) atomicAdd(&pk[b * (KMS_WORDS + 1) + wl], c << (8u * q));    // (G <= 256: a quarter's count fits its byte)
+                }
+            }
         }
-        for (; g < g1; ++g) c += (m[(size_t)g * W] >> sh) & 1u;
-        total += c;
-        pack |= c << ((8u * q) & 31u);
     }
-    const uint64_t idx = (x % P) * slots + x / P;
-    counts[idx] = total;
-    if (qpack) qpack[idx] = pack;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < NK; i += NT) {
+        const uint64_t x = (uint64_t)blockIdx.x * NK + i;
+        if (x < T) {
+            const uint64_t idx = (x % P) * slots + x / P;
+            const uint32_t at = (i & 31u) * (KMS_WORDS + 1) + (i >> 5);
+            counts[idx] = tot[at];
+            if (qpack) qpack[idx] = pk[at];
+        }
+    }
 }
 
 // ---- generic exclusive scan of u32 -> u64 (three kernels) -------------------------------------
@@ -277,6 +312,10 @@ __global__ __launch_bounds__(256) void km_write_kernel(const uint32_t* __restric
 // lane-contiguous run through an 80-entry LDS buffer per wavefront (the new entries sit in lanes by group, with holes), the run is
 // stored up to its last line boundary -- full, aligned lines only, but for a key's very first and very last store -- and the rest
 // becomes the new tail.  Same entries at the same positions as km_write_kernel.
+// NTS: the stores of whole lines are non-temporal -- the entries are written once and read by nothing in the call, and stores that
+// do not claim L2 lines ran 7 % faster here; the two stores per key that may touch a line partly stay
+// plain, so that L2 can merge them with the neighbouring key's.  debug_flags bit 14 keeps every store plain, for the comparison.
+template <bool NTS>
 __global__ __launch_bounds__(256) void km_write_lines_kernel(const uint32_t* __restrict__ table, uint64_t T, uint32_t G,
                                                              const uint32_t* __restrict__ branch_of_group, uint32_t P,
                                                              uint64_t slots, uint64_t* __restrict__ cursor,
@@ -346,8 +385,12 @@ __global__ __launch_bounds__(256) void km_write_lines_kernel(const uint32_t* __r
             if (cut) {
                 uint2* const d = entries + pos[t];
                 const uint64_t m0 = cut >= 64 ? ~0ull : ((1ull << cut) - 1ull);
-                store8_lanes(d, lane8, e0.x, e0.y, m0);
-                if (cut > 64) store8_lanes<512>(d, lane8, e1.x, e1.y, (1ull << (cut - 64)) - 1ull);
+                auto put = [&](auto nt) {
+                    store8_lanes<0, decltype(nt)::value>(d, lane8, e0.x, e0.y, m0);
+                    if (cut > 64) store8_lanes<512, decltype(nt)::value>(d, lane8, e1.x, e1.y, (1ull << (cut - 64)) - 1ull);
+                };
+                // (a key's first store of a call starts inside a line: that one stays a plain store, like the last)
+                if (NTS && (pos[t] & 15u) == 0) put(std::true_type{}); else put(std::false_type{});
             }
             tbr[t] = er.x; tsc[t] = er.y;                    // lanes < rem: the new tail
             tl[t] = rem;
