@@ -114,7 +114,8 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * kernels keep in LDS is scored in slices instead of failing the call -- see "Not supported" above; applies to every scoring entry
  * point: per-branch result, key-major with and without owners or positions, key-range passes, ipkgpu_score_groups_positions, the
  * pieces of the on-disk build; results of calls without such a window do not change);
- * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "release_workspaces" (any value: the context's workspaces and cached result
+ * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "db_load_chunk_bytes" (bytes of each of the two pinned buffers a file passes
+ * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
  * Every variant yields identical results.  Returns IPKGPU_ERR_INVALID for unknown names.
  *
@@ -354,7 +355,7 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
  * first drops the cached blocks and, if it still would, fails with IPKGPU_ERR_NOMEM; work sized by free device memory sees at most what
  * the budget leaves.  The context stays usable after such a failure.  Device memory of the caller (the matrices) is not counted. */
 int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak);
-/* Reads back "workspace_bytes", "device_budget_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
+/* Reads back "workspace_bytes", "device_budget_bytes", "db_load_chunk_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
  * "debug_sliced_windows" (the windows this context has scored in slices so far), "debug_pool_bytes" (the bytes its pair pool holds), or "last_refused_bytes":
  * the bytes held plus the size of the last allocation the device or the budget refused -- what the failed step needed at least.
  * IPKGPU_ERR_INVALID for other names. */
@@ -523,6 +524,85 @@ double ipkgpu_db_write_time_s(const ipkgpu_ctx* ctx, int which);
  * width and value are guesses (ipk_format.hpp); IPKGPU_IPK_PROTOCOL_VERSION in the environment sets the value, 0 = neither field
  * is written.  Readers of this library's files (ipkgpu_db_merge_files, the tests' parser) ask here what to expect. */
 uint32_t ipkgpu_db_protocol_version(void);
+
+/* ---- reading a database file back: description and validation on the host, the load on the device ----------------------
+ * The reference loads a database with i2l::load and ships two tools over the loaded object, ipkdiff and ipkdump
+ * (tools/src/diff.cpp, tools/src/dump.cpp); `ipk.py diff` / `ipk.py dump` are this library's.  The layout read is the one the
+ * writers above write (ipk_format.hpp: a reconstruction, NOT pinned against a real .ipk -- reading a real .ipk is not claimed),
+ * under the protocol version of the running process (ipkgpu_db_protocol_version); a file of another one is refused. */
+typedef struct ipkgpu_db_file ipkgpu_db_file;
+
+/* Parses and validates everything in front of the first k-mer record (host only, no GPU).  IPKGPU_ERR_INVALID with
+ * ipkgpu_db_file_last_error() (this thread's last failing ipkgpu_db_file_* call) if the file is not of the layout. */
+int ipkgpu_db_file_open(const char* path, ipkgpu_db_file** out);
+void ipkgpu_db_file_close(ipkgpu_db_file* f);
+const char* ipkgpu_db_file_last_error(void);
+/* The head's fields; strings and arrays are owned by the handle. */
+const char* ipkgpu_db_file_sequence_type(const ipkgpu_db_file* f);
+int ipkgpu_db_file_positions_loaded(const ipkgpu_db_file* f);           /* the positions flag (0 where the layout has none) */
+uint32_t ipkgpu_db_file_protocol_version(const ipkgpu_db_file* f);       /* the protocol word (0 where the layout has none) */
+uint32_t ipkgpu_db_file_library_version(const ipkgpu_db_file* f);        /* the archive preamble's library version */
+uint64_t ipkgpu_db_file_tree_index_size(const ipkgpu_db_file* f);
+const uint32_t* ipkgpu_db_file_tree_num_nodes(const ipkgpu_db_file* f);  /* [tree_index_size] */
+const double* ipkgpu_db_file_tree_subtree_length(const ipkgpu_db_file* f);
+const char* ipkgpu_db_file_newick(const ipkgpu_db_file* f);
+uint64_t ipkgpu_db_file_kmer_size(const ipkgpu_db_file* f);
+float ipkgpu_db_file_omega(const ipkgpu_db_file* f);
+uint64_t ipkgpu_db_file_total_kmers(const ipkgpu_db_file* f);            /* the header's totals, as written */
+uint64_t ipkgpu_db_file_total_entries(const ipkgpu_db_file* f);
+uint64_t ipkgpu_db_file_bytes(const ipkgpu_db_file* f);                  /* size of the file */
+uint64_t ipkgpu_db_file_body_offset(const ipkgpu_db_file* f);            /* where the first k-mer record starts */
+/* The head as the writers take it (pointers into the handle): ipkgpu_db_write(ctx, loaded, &h, ...) reproduces the file. */
+int ipkgpu_db_file_header(const ipkgpu_db_file* f, ipkgpu_db_header* h);
+/* Walks the records by their count fields (16 + 8 n bytes each, 16 + 10 n with positions): the one serial part of reading a
+ * file, streamed once.  IPKGPU_ERR_INVALID, the message naming the record's index and its byte offset in the file, when a count
+ * would carry a record past the end of the file, when the walk does not end exactly at the end of the file, or when the numbers
+ * of records or entries differ from the header's totals. */
+int ipkgpu_db_file_check(ipkgpu_db_file* f, uint64_t* n_records, uint64_t* n_entries);
+
+/* Loads a database file onto the device: the same object the builds produce (every accessor, ipkgpu_db_write included, takes it).
+ * keys ascending, key_offsets, entries in the file's order inside a key, positions for a positioned file; the filter arrays hold
+ * the file's filter values (ipkgpu_db_filter_values: their bits; _f64: their widening) and the file's record order
+ * (ipkgpu_db_filter_order: keys[order[i]] is the i-th record), so ipkgpu_db_write with ipkgpu_db_file_header(ipkgpu_db_header_of(d))
+ * gives the file back byte for byte.
+ * The file goes chunk by chunk through the context's two pinned buffers (option "db_load_chunk_bytes"; 0 = 64 MiB, the spill
+ * blocks') into a device image of its body, the next read under the previous copy, while the host walks the count fields
+ * (ipkgpu_db_file_check's walk); then db_unpack_heads_kernel, a sort of (key, record), a scan of the counts and
+ * db_unpack_entries_kernel (kernels_dbload.hpp).  No kernel indexes by a number of the file the host has not checked: a bad file
+ * is IPKGPU_ERR_INVALID before the first of them is launched.  Also IPKGPU_ERR_INVALID: a key in two records, more than
+ * 2^32 - 1 records, a record of 2^32 entries or more.  Device memory: the image (the body's bytes, freed before the call returns)
+ * plus the database plus 44 bytes per k-mer of workspace and the sort's own, all counted by ipkgpu_mem_stats and held to "device_budget_bytes";
+ * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded in pieces. */
+int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out);
+/* The head of the file a database was loaded from (owned by the database); NULL for databases that were not loaded. */
+const ipkgpu_db_file* ipkgpu_db_header_of(const ipkgpu_db* d);
+/* The last ipkgpu_db_load of this context: 0 = seconds in all, 1 = file reads, 2 = the host's walk, 3 = waiting for the device;
+ * 4 = db_unpack_heads_kernel ms, 5 = db_unpack_entries_kernel ms, 6 = all device work behind the last copy, ms. */
+double ipkgpu_db_load_time(const ipkgpu_ctx* ctx, int which);
+
+/* ipkdiff's comparison of two databases of one context (tools/src/diff.cpp:210-295), on the device (kernels_dbdiff.hpp). */
+typedef struct ipkgpu_db_diff_counts {
+    uint64_t keys_a, keys_b, keys_only_a, keys_only_b;
+    uint64_t entries_a, entries_b;
+    uint64_t entries_only_a, entries_only_b;      /* (k-mer, branch) scored in one database only; includes those of keys_only_* */
+    uint64_t scores_differ;                        /* (k-mer, branch) in both, scores do not match */
+    uint64_t positions_differ;                     /* both positioned, scores match, positions differ; else 0 */
+    double   max_abs_diff;                         /* over (k-mer, branch) pairs present in both */
+} ipkgpu_db_diff_counts;
+typedef struct ipkgpu_db_diff_record { uint32_t key, branch; float a_score, b_score; } ipkgpu_db_diff_record;  /* NaN = not scored */
+/* Scores of a (k-mer, branch) in both match iff fabs(a - b) < eps -- the difference in float, the comparison in double (:233);
+ * eps == 0: iff the score bits are equal.  An entry is matched with the FIRST entry of the same branch in the other database's
+ * list of that k-mer (the files of this library name a branch once per k-mer; where the two lists of a k-mer name the same branches
+ * in the same order they are compared place by place); the order of a k-mer's entries carries no meaning.  max_abs_diff is taken
+ * over A's entries that B scores too.  records (may be NULL with max_records == 0) receives the first max_records differences --
+ * entries scored in one database only, and scores that do not match -- in this order: ascending k-mer; inside a k-mer A's entries
+ * in A's order, then B's entries A does not score in B's order.  *n_records = how many were written; the counts are exact
+ * whatever max_records is.  ipkgpu_db_diff_time_ms: device time of the context's last call. */
+int ipkgpu_db_diff(ipkgpu_ctx* ctx, const ipkgpu_db* a, const ipkgpu_db* b, double eps,
+                   ipkgpu_db_diff_counts* counts, ipkgpu_db_diff_record* records, uint64_t max_records, uint64_t* n_records);
+double ipkgpu_db_diff_time_ms(const ipkgpu_ctx* ctx);
+/* DB_DIFF_CHUNK: the entries of a list the general path of ipkgpu_db_diff keeps in LDS at a time (tests build a longer list). */
+uint32_t ipkgpu_db_diff_chunk(void);
 
 #ifdef __cplusplus
 }

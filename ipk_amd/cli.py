@@ -13,6 +13,8 @@ Alignment reduction/extension and RUNNING the ancestral reconstruction are IPK's
 `ipk.py build --ar-only` of the reference, or raxml-ng run on the saved extended tree).
 
   ipk.py build -r aln.fasta -t tree.nwk -w work --ar-dir work/AR -k 10
+  ipk.py diff [-v] [--eps 1e-2 | --exact] A.ipk B.ipk          (the reference's ipkdiff; exit status 1 on a difference)
+  ipk.py dump [--limit N] DB.ipk                               (the reference's ipkdump)
 
 --mapping (optional, not in the reference): TSV `ar_node_label <TAB> branch_postorder_id` per ghost node in scoring order;
 replaces the tree-derived plan (synthetic inputs without trees).
@@ -269,6 +271,140 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     db.free(); parts.free(); eng.close(); arp.close()
     if world > 1 and own_group:
         dist.destroy_process_group()
+
+
+# ---- looking into database files: the reference's tools ipkdiff / ipkdump (tools/src/diff.cpp, tools/src/dump.cpp) -----------------
+
+_ALPHABET = {"DNA": ("ACGT", 2), "AA": ("RHKDESTNQCGPAILMFWYV", 5)}       # IPK's code order (AA: ar.cpp:227-234), bits per symbol
+
+
+def decode_kmer(key, k, sequence_type):
+    """i2l::decode_kmer: the k symbols of a packed code, first symbol in the highest bits (pk_compute.cpp:96-104)."""
+    letters, bits = _ALPHABET[sequence_type]
+    return "".join(letters[(int(key) >> (bits * (k - 1 - i))) & ((1 << bits) - 1)] for i in range(k))
+
+
+def preorder_ids(newick):
+    """post-order id -> pre-order id (root 0, children in file order) of the header's tree."""
+    from ipk_amd import tree as T
+    t = T.Tree.parse(newick)
+    n = t.num_nodes
+    kids = [[] for _ in range(n)]
+    root = n - 1
+    for i in range(n):
+        p = t.parent(i)
+        if p < 0:
+            root = i
+        else:
+            kids[p].append(i)                      # (ascending post-order id = file order among siblings)
+    pre, stack, nxt = [0] * n, [root], 0
+    while stack:
+        v = stack.pop()
+        pre[v] = nxt
+        nxt += 1
+        stack.extend(reversed(kids[v]))
+    t.close()
+    return pre
+
+
+def _g(x):
+    return "%g" % x                                 # what `std::cout << double` prints
+
+
+@ipk.command()
+@click.option("-v", "--verbose", is_flag=True, help="also print the differing (k-mer, branch) pairs: code, k-mer, branch, 10^A, 10^B ('-' = not scored)")
+@click.option("--eps", type=float, default=1e-2, show_default=True, help="scores match iff |a - b| < eps (the reference's constant, diff.cpp:212)")
+@click.option("--exact", is_flag=True, help="scores match iff their bits are equal (eps = 0)")
+@click.option("--max-records", type=int, default=100, show_default=True, help="with -v: print at most this many pairs (the counts are exact anyway)")
+@click.option("--device", type=int, default=0, show_default=True, help="GPU index")
+@click.argument("a", type=click.Path(exists=True, dir_okay=False))
+@click.argument("b", type=click.Path(exists=True, dir_okay=False))
+def diff(verbose, eps, exact, max_records, device, a, b):
+    """Compares two database files (the reference's ipkdiff): both are loaded onto the GPU and compared there.
+
+    Prints the reference's lines in its order, tab separated, each with OK or DIFF and the two values.  Deviations from the
+    reference's tool: `Tree index` is really compared (the reference prints ???); `Position support` is printed (commented out there);
+    two positioned files also get a `Phylo-k-mer positions` line (equal scores, different positions); the k-mers of the verbose list
+    come in ascending order; and the exit status is 1 when any line says DIFF -- the reference's ipkdiff always returns 0
+    (diff.cpp:115-116)."""
+    import ipk_amd
+    eng = ipk_amd.Engine(device)
+    try:
+        da, db_ = eng.load_db(a), eng.load_db(b)
+        ha, hb = da.header, db_.header
+        all_ok = True
+
+        def line(name, va, vb, match=None, show=True):
+            nonlocal all_ok
+            match = (va == vb) if match is None else match
+            all_ok &= bool(match)
+            click.echo(f"{name}:\t{'OK' if match else 'DIFF'}\t" + (f"{va}\t{vb}" if show else " \t "))
+
+        def log_eps(h):
+            sigma = {"DNA": 4, "AA": 20}.get(h["sequence_type"])
+            return _g(ipk_amd.log_threshold(h["omega"], sigma, h["kmer_size"])) if sigma and h["kmer_size"] else "?"
+
+        line("Sequence type", ha["sequence_type"], hb["sequence_type"])
+        line("Position support", str(ha["positions_loaded"]).lower(), str(hb["positions_loaded"]).lower())
+        line("Protocol version", ha["protocol_version"], hb["protocol_version"])
+        line("k-mer size", ha["kmer_size"], hb["kmer_size"])
+        same_omega = ha["omega"] == hb["omega"]
+        line("Omega", _g(ha["omega"]), _g(hb["omega"]), same_omega)
+        line("Threshold", log_eps(ha), log_eps(hb), same_omega and ha["kmer_size"] == hb["kmer_size"] and ha["sequence_type"] == hb["sequence_type"])
+        line("Reference tree", None, None, ha["newick"] == hb["newick"], show=False)
+        line("Tree index", len(ha["tree_index"]), len(hb["tree_index"]), ha["tree_index"] == hb["tree_index"])
+        c, rec = eng.diff_dbs(da, db_, eps=0.0 if exact else eps, max_records=max_records if verbose else 0)
+        line("Number of k-mers", c["keys_a"], c["keys_b"])
+        line("Number of phylo-k-mers", c["entries_a"], c["entries_b"])
+        n_diffs = c["entries_only_a"] + c["entries_only_b"] + c["scores_differ"]
+        all_ok &= n_diffs == 0
+        click.echo(f"Phylo-k-mer scores:\t{'OK' if n_diffs == 0 else 'DIFF'}\t{n_diffs}")
+        if ha["positions_loaded"] and hb["positions_loaded"]:
+            all_ok &= c["positions_differ"] == 0
+            click.echo(f"Phylo-k-mer positions:\t{'OK' if c['positions_differ'] == 0 else 'DIFF'}\t{c['positions_differ']}")
+        if verbose:
+            click.echo("\t\tcode\tk-mer\tbranch\tA score\tB score")
+            k, st = ha["kmer_size"], ha["sequence_type"]
+            val = lambda x: "-" if np.isnan(x) else _g(10.0 ** float(x))
+            for r in rec:
+                kmer = decode_kmer(r["key"], k, st) if st in _ALPHABET else "?"
+                click.echo(f"\t\t{int(r['key'])}\t{kmer}\t{int(r['branch'])}\t{val(r['a_score'])}\t{val(r['b_score'])}\t")
+        da.free(); db_.free()
+    finally:
+        eng.close()
+    sys.exit(0 if all_ok else 1)
+
+
+@ipk.command()
+@click.option("--limit", type=int, default=None, help="print only the first N k-mers of the file [all]")
+@click.option("--device", type=int, default=0, show_default=True, help="GPU index")
+@click.argument("db", type=click.Path(exists=True, dir_okay=False))
+def dump(limit, device, db):
+    """Prints a database file as text (the reference's ipkdump), in the file's record order.
+
+    Per k-mer one line with the decoded k-mer, then one line per entry: TAB 10^score (as %g) TAB pre-order id of the branch in the
+    header's tree (root 0, children in file order), and TAB window position for a positioned file.  A file without a tree in its
+    header (a shard) prints the branch's post-order id as stored."""
+    import ipk_amd
+    eng = ipk_amd.Engine(device)
+    try:
+        d = eng.load_db(db)
+        h = d.header
+        pre = preorder_ids(h["newick"]) if h["newick"] else None
+        keys, off, order = d.keys(), d.key_offsets(), d.filter_order()
+        br, sc = d.entries()
+        pos = d.positions()
+        out = []
+        for i in (order if limit is None else order[:max(limit, 0)]):
+            out.append(decode_kmer(keys[i], h["kmer_size"], h["sequence_type"]))
+            for j in range(int(off[i]), int(off[i + 1])):
+                b = int(br[j])
+                node = pre[b] if pre is not None and b < len(pre) else b
+                out.append(f"\t{_g(10.0 ** float(sc[j]))}\t{node}" + (f"\t{int(pos[j])}" if pos is not None else ""))
+        click.echo("\n".join(out))
+        d.free()
+    finally:
+        eng.close()
 
 
 if __name__ == "__main__":

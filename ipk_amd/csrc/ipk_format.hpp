@@ -28,6 +28,7 @@
 // library version, u64/f64 tree index, f32 filter value and u32 key widths.  IPKGPU_IPK_PROTOCOL_VERSION=0 leaves both fields out
 // (the round-3 layout); any other value is written as given.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -108,25 +109,128 @@ inline bool skip_string(FILE* f, uint64_t limit = (uint64_t)1 << 32)
     uint64_t n = 0;
     return get_v(f, n) && n <= limit && fseek(f, (long)n, SEEK_CUR) == 0;
 }
-// Positions `f` at the first k-mer record; the header's totals come back, and with positions_loaded the positions flag (false where
-// the layout has none: protocol version 0).  false: not a file of this layout (as written by
-// this process: the protocol word is expected exactly when protocol_version() is non-zero, and must hold that value).
-inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries, bool* positions_loaded = nullptr)
+inline bool get_string(FILE* f, std::string& s, uint64_t limit)
+{
+    uint64_t n = 0;
+    if (!get_v(f, n) || n > limit) return false;
+    s.resize((size_t)n);
+    return get(f, &s[0], (size_t)n);
+}
+// everything file_head wrote, and where the first k-mer record starts
+struct Head {
+    uint16_t library_version = 0;
+    uint32_t protocol = 0;                   // 0: the layout without protocol word and positions flag
+    std::string sequence_type;
+    bool positions_loaded = false;
+    std::vector<uint32_t> tree_num_nodes;    // (u64 in the file; the writers take u32, and a larger value is refused)
+    std::vector<double> tree_subtree_length;
+    std::string newick;
+    uint64_t kmer_size = 0;
+    float omega = 0;
+    uint64_t total_kmers = 0, total_entries = 0;
+    uint64_t body_at = 0;                    // file offset of the first record
+};
+// Positions `f` at the first k-mer record and fills `h`.  Returns nullptr, or what is wrong with the file: not a file of this layout
+// as written by this process (the protocol word is expected exactly when protocol_version() is non-zero, and must hold that value).
+// `limit`: no string or array of the head may claim more bytes than this (the file's size).
+inline const char* read_head_full(FILE* f, Head& h, uint64_t limit = (uint64_t)1 << 32)
 {
     uint64_t n = 0;
     char magic[22];
-    if (!get_v(f, n) || n != 22 || !get(f, magic, 22) || memcmp(magic, "serialization::archive", 22) != 0) return false;
-    uint16_t ver; uint8_t sz[4]; int32_t one;
-    if (!get_v(f, ver) || !get(f, sz, 4) || !get_v(f, one) || sz[0] != 4 || sz[1] != 8 || sz[2] != 4 || sz[3] != 8 || one != 1) return false;
-    uint64_t n_index = 0, kmer_size = 0; float omega = 0;
+    if (!get_v(f, n) || n != 22 || !get(f, magic, 22) || memcmp(magic, "serialization::archive", 22) != 0) return "no archive preamble";
+    uint8_t sz[4]; int32_t one;
+    if (!get_v(f, h.library_version) || !get(f, sz, 4) || !get_v(f, one) || sz[0] != 4 || sz[1] != 8 || sz[2] != 4 || sz[3] != 8 || one != 1)
+        return "not an x86-64 binary archive";
     const uint32_t proto = protocol_version();
-    uint32_t got = 0; uint8_t positions = 0;
-    if (proto && (!get_v(f, got) || got != proto)) return false;
-    if (!skip_string(f) || (proto && (!get_v(f, positions) || positions > 1)) || !get_v(f, n_index) || n_index > ((uint64_t)1 << 32) || fseek(f, (long)(n_index * 16), SEEK_CUR) != 0) return false;
-    if (!skip_string(f) || !get_v(f, kmer_size) || !get_v(f, omega)) return false;
-    if (positions_loaded) *positions_loaded = positions != 0;
-    return get_v(f, total_kmers) && get_v(f, total_entries);
+    uint8_t positions = 0;
+    h.protocol = 0;
+    if (proto && (!get_v(f, h.protocol) || h.protocol != proto)) return "protocol version differs from this process'";
+    if (!get_string(f, h.sequence_type, std::min<uint64_t>(limit, 64))) return "bad sequence type";
+    if (proto && (!get_v(f, positions) || positions > 1)) return "bad positions flag";
+    h.positions_loaded = positions != 0;
+    uint64_t n_index = 0;
+    if (!get_v(f, n_index) || n_index > limit / 16) return "bad tree index size";
+    h.tree_num_nodes.resize((size_t)n_index); h.tree_subtree_length.resize((size_t)n_index);
+    for (uint64_t i = 0; i < n_index; ++i) {
+        uint64_t nn = 0;
+        if (!get_v(f, nn) || !get_v(f, h.tree_subtree_length[i])) return "tree index cut short";
+        if (nn > 0xFFFFFFFFull) return "tree index entry beyond 32 bits";
+        h.tree_num_nodes[i] = (uint32_t)nn;
+    }
+    if (!get_string(f, h.newick, limit)) return "bad newick string";
+    if (!get_v(f, h.kmer_size) || !get_v(f, h.omega) || !get_v(f, h.total_kmers) || !get_v(f, h.total_entries)) return "head cut short";
+    const long at = ftell(f);
+    if (at < 0) return "cannot tell the file position";
+    h.body_at = (uint64_t)at;
+    return nullptr;
 }
+// The totals and the positions flag alone (the shard files of a multi-GPU build): false where read_head_full refuses the file.
+inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries, bool* positions_loaded = nullptr)
+{
+    Head h;
+    if (read_head_full(f, h)) return false;
+    total_kmers = h.total_kmers; total_entries = h.total_entries;
+    if (positions_loaded) *positions_loaded = h.positions_loaded;
+    return true;
+}
+
+// ---- the walk over the k-mer records: the only serial part of reading a file ----------------------------------------------------
+// The body's bytes are fed in order, in chunks of any size (a head may straddle two); only the count fields are looked at.  Kept:
+// every record's start (body-relative) and the totals.  A count that would carry its record past the end of the body stops the
+// walk with a message naming the record and its byte offset in the FILE, before anything could index by it.
+struct RecordWalker {
+    uint64_t body_at = 0, body_bytes = 0, entry_bytes = ENTRY_BYTES, max_records = ~(uint64_t)0;
+    uint64_t pos = 0;                        // start of the record whose head is being collected
+    uint64_t n_entries = 0, max_count = 0;
+    std::vector<uint64_t> starts;
+    uint8_t carry[RECORD_HEAD_BYTES]; uint32_t carry_n = 0;
+    std::string error;
+    void begin(uint64_t body_at_, uint64_t body_bytes_, bool positions, uint64_t max_records_)
+    {
+        body_at = body_at_; body_bytes = body_bytes_; entry_bytes = positions ? ENTRY_POS_BYTES : ENTRY_BYTES; max_records = max_records_;
+        pos = 0; n_entries = 0; max_count = 0; carry_n = 0; starts.clear(); error.clear();
+    }
+    bool fail_at(const char* what, uint64_t count)
+    {
+        char b[256];
+        snprintf(b, sizeof b, "record %llu at byte offset %llu: %s (count field %llu)", (unsigned long long)starts.size(),
+                 (unsigned long long)(body_at + pos), what, (unsigned long long)count);
+        error = b;
+        return false;
+    }
+    // body bytes [lo, hi) at `data`; chunks follow each other without gaps
+    bool feed(const uint8_t* data, uint64_t lo, uint64_t hi)
+    {
+        while (pos + carry_n < hi) {
+            const uint64_t at = pos + carry_n;
+            const uint32_t take = (uint32_t)std::min<uint64_t>(RECORD_HEAD_BYTES - carry_n, hi - at);
+            memcpy(carry + carry_n, data + (at - lo), take);
+            carry_n += take;
+            if (carry_n < RECORD_HEAD_BYTES) break;
+            uint64_t count;
+            memcpy(&count, carry + 8, 8);
+            if (starts.size() >= max_records) return fail_at("more records than the header's total", count);
+            if (count > (body_bytes - pos - RECORD_HEAD_BYTES) / entry_bytes) return fail_at("its entries would end past the end of the file", count);
+            starts.push_back(pos);
+            n_entries += count; max_count = std::max(max_count, count);
+            pos += RECORD_HEAD_BYTES + entry_bytes * count;
+            carry_n = 0;
+        }
+        return true;
+    }
+    bool finish(uint64_t total_kmers, uint64_t total_entries)
+    {
+        if (pos != body_bytes) return fail_at("the file ends inside the record's head", 0);
+        if (starts.size() != total_kmers || n_entries != total_entries) {
+            char b[256];
+            snprintf(b, sizeof b, "the records' walk found %llu k-mers and %llu entries, the header's totals are %llu and %llu",
+                     (unsigned long long)starts.size(), (unsigned long long)n_entries, (unsigned long long)total_kmers, (unsigned long long)total_entries);
+            error = b;
+            return false;
+        }
+        return true;
+    }
+};
 // the order of the k-mer records: ascending filter value (as an order-preserving integer code of the float), ties by
 // ascending key -- kernels_filter.hpp's sort key, db_builder.cpp:281-284 (`std::sort` over kmer_fv)
 inline uint64_t record_sort_key(uint32_t key, uint32_t fv_bits)

@@ -41,6 +41,9 @@
 #include "kernels_filter.hpp"
 #include "kernels_dbfile.hpp"
 #include "kernels_spill.hpp"
+#include "kernels_dbload.hpp"
+#include "kernels_dbdiff.hpp"
+#include "db_file.hpp"
 #include "spill_format.hpp"
 #include <sys/stat.h>
 #include <chrono>
@@ -167,6 +170,9 @@ struct ipkgpu_ctx {
     } pend;
     uint64_t last_entries = 0; uint32_t last_gb = 0;   // the key-major writer's output of the previous batch: the next one's estimate
     double t_write_total = 0, t_write_device = 0, t_write_file = 0;   // last ipkgpu_db_write
+    int64_t opt_load_chunk = 0;          // "db_load_chunk_bytes": bytes per pinned buffer of ipkgpu_db_load (0: SPILL_STAGE, the spill blocks')
+    double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
+    double t_diff_ms = 0;
     int num_cu = 256;
 };
 
@@ -229,6 +235,7 @@ struct ipkgpu_db {
     std::vector<uint32_t> h_order;
     bool h_filter_ok = false;
     double t_filter = 0;
+    ipkgpu_db_file* file = nullptr;           // ipkgpu_db_load: the head of the file the database came from (owned)
 };
 
 static std::string g_create_err;
@@ -506,6 +513,11 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
     if (!strcmp(name, "slice_long_lists")) {
         if (value != 0 && value != 1) return fail(ctx, IPKGPU_ERR_INVALID, "slice_long_lists is 0 or 1");
         ctx->opt_slice = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "db_load_chunk_bytes")) {
+        if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "db_load_chunk_bytes must not be negative (0 = the default)");
+        ctx->opt_load_chunk = value;
         return IPKGPU_OK;
     }
     if (!strcmp(name, "variant")) { ctx->opt_variant = value; return IPKGPU_OK; }
@@ -2856,6 +2868,7 @@ void ipkgpu_db_free(ipkgpu_db* d)
         ctx_release(d->ctx, d->d_positions);
         ctx_release(d->ctx, d->d_fv64); ctx_release(d->ctx, d->d_fv32); ctx_release(d->ctx, d->d_order);
     }
+    ipkgpu_db_file_close(d->file);
     delete d;
 }
 
@@ -3155,6 +3168,7 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "device_budget_bytes")) { *value = ctx->budget; return IPKGPU_OK; }
     if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
     if (!strcmp(name, "slice_long_lists")) { *value = ctx->opt_slice; return IPKGPU_OK; }
+    if (!strcmp(name, "db_load_chunk_bytes")) { *value = ctx->opt_load_chunk; return IPKGPU_OK; }
     if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
     if (!strcmp(name, "debug_pool_bytes")) { *value = (int64_t)ctx->pool.cap; return IPKGPU_OK; }   // bytes the pair pool holds (tests)
     return IPKGPU_ERR_INVALID;
@@ -3373,4 +3387,5 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 
 }  // extern "C"
 
+#include "db_load.hpp"
 #include "comm_rccl.hpp"

@@ -7,6 +7,7 @@ it is written by ipkgpu_db_write (streamed from the device: every build path, fi
 (host arrays: the C ABI's host serialiser and the tests' yardstick).  This module calls both and parses the layout back for the tests.
 """
 import ctypes as C
+import os
 import struct
 
 import numpy as np
@@ -14,7 +15,12 @@ import numpy as np
 from .engine import IpkGpuError, load_library
 
 ABI_SYMBOLS = ["ipkgpu_db_write", "ipkgpu_db_write_host", "ipkgpu_db_write_host_positions", "ipkgpu_db_write_last_error", "ipkgpu_db_write_time_s",
-               "ipkgpu_db_merge_files", "ipkgpu_db_merge_last_error", "ipkgpu_db_protocol_version"]
+               "ipkgpu_db_merge_files", "ipkgpu_db_merge_last_error", "ipkgpu_db_protocol_version",
+               "ipkgpu_db_file_open", "ipkgpu_db_file_close", "ipkgpu_db_file_last_error", "ipkgpu_db_file_check", "ipkgpu_db_file_header",
+               "ipkgpu_db_file_sequence_type", "ipkgpu_db_file_positions_loaded", "ipkgpu_db_file_protocol_version",
+               "ipkgpu_db_file_library_version", "ipkgpu_db_file_tree_index_size", "ipkgpu_db_file_tree_num_nodes",
+               "ipkgpu_db_file_tree_subtree_length", "ipkgpu_db_file_newick", "ipkgpu_db_file_kmer_size", "ipkgpu_db_file_omega",
+               "ipkgpu_db_file_total_kmers", "ipkgpu_db_file_total_entries", "ipkgpu_db_file_bytes", "ipkgpu_db_file_body_offset"]
 _bound = False
 
 
@@ -47,6 +53,24 @@ def _lib():
         L.ipkgpu_db_merge_last_error.argtypes = []
         L.ipkgpu_db_protocol_version.restype = C.c_uint32
         L.ipkgpu_db_protocol_version.argtypes = []
+        L.ipkgpu_db_file_open.restype = C.c_int
+        L.ipkgpu_db_file_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.ipkgpu_db_file_close.restype = None
+        L.ipkgpu_db_file_close.argtypes = [C.c_void_p]
+        L.ipkgpu_db_file_last_error.restype = C.c_char_p
+        L.ipkgpu_db_file_last_error.argtypes = []
+        L.ipkgpu_db_file_check.restype = C.c_int
+        L.ipkgpu_db_file_check.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ipkgpu_db_file_header.restype = C.c_int
+        L.ipkgpu_db_file_header.argtypes = [C.c_void_p, C.POINTER(_Header)]
+        for name, t in (("sequence_type", C.c_char_p), ("positions_loaded", C.c_int), ("protocol_version", C.c_uint32),
+                        ("library_version", C.c_uint32), ("tree_index_size", C.c_uint64), ("tree_num_nodes", C.POINTER(C.c_uint32)),
+                        ("tree_subtree_length", C.POINTER(C.c_double)), ("newick", C.c_char_p), ("kmer_size", C.c_uint64),
+                        ("omega", C.c_float), ("total_kmers", C.c_uint64), ("total_entries", C.c_uint64), ("bytes", C.c_uint64),
+                        ("body_offset", C.c_uint64)):
+            fn = getattr(L, "ipkgpu_db_file_" + name)
+            fn.restype = t
+            fn.argtypes = [C.c_void_p]
         _bound = True
     return L
 
@@ -146,6 +170,57 @@ def write_db_positions(path, sequence_type, tree_index, newick, kmer_size, omega
 def protocol_version():
     """What the writers put behind the archive preamble (0: no protocol word, no positions flag); ipk_format.hpp."""
     return int(_lib().ipkgpu_db_protocol_version())
+
+
+def info_of_handle(h):
+    """The head of an open ipkgpu_db_file as the dict read_db returns, plus file_bytes and body_offset."""
+    L = _lib()
+    n = int(L.ipkgpu_db_file_tree_index_size(h))
+    nn, sl = L.ipkgpu_db_file_tree_num_nodes(h), L.ipkgpu_db_file_tree_subtree_length(h)
+    return dict(sequence_type=L.ipkgpu_db_file_sequence_type(h).decode(), tree_index=[(int(nn[i]), float(sl[i])) for i in range(n)],
+                newick=L.ipkgpu_db_file_newick(h).decode(), kmer_size=int(L.ipkgpu_db_file_kmer_size(h)),
+                omega=float(L.ipkgpu_db_file_omega(h)), total_num_kmers=int(L.ipkgpu_db_file_total_kmers(h)),
+                total_num_entries=int(L.ipkgpu_db_file_total_entries(h)), library_version=int(L.ipkgpu_db_file_library_version(h)),
+                protocol_version=int(L.ipkgpu_db_file_protocol_version(h)), positions_loaded=bool(L.ipkgpu_db_file_positions_loaded(h)),
+                file_bytes=int(L.ipkgpu_db_file_bytes(h)), body_offset=int(L.ipkgpu_db_file_body_offset(h)))
+
+
+def header_args(info):
+    """The writers' header arguments out of a file_info / Db.header dict."""
+    return dict(sequence_type=info["sequence_type"], tree_index=info["tree_index"], newick=info["newick"], kmer_size=info["kmer_size"],
+                omega=info["omega"])
+
+
+def _open(path):
+    L = _lib()
+    h = C.c_void_p()
+    rc = L.ipkgpu_db_file_open(os.fsencode(path), C.byref(h))
+    if rc != 0:
+        raise IpkGpuError(rc, L.ipkgpu_db_file_last_error().decode())
+    return L, h
+
+
+def file_info(path):
+    """ipkgpu_db_file_open: every field of the file's head (host only, no walk over the records) -- the dict read_db returns."""
+    L, h = _open(path)
+    try:
+        return info_of_handle(h)
+    finally:
+        L.ipkgpu_db_file_close(h)
+
+
+def check_file(path):
+    """ipkgpu_db_file_check: walks the records by their count fields; returns (records, entries) or raises IpkGpuError with the record
+    index and byte offset where the file stops being one (truncated, a bad count, totals that differ from the header's)."""
+    L, h = _open(path)
+    try:
+        nr, ne = C.c_uint64(0), C.c_uint64(0)
+        rc = L.ipkgpu_db_file_check(h, C.byref(nr), C.byref(ne))
+        if rc != 0:
+            raise IpkGpuError(rc, L.ipkgpu_db_file_last_error().decode())
+        return int(nr.value), int(ne.value)
+    finally:
+        L.ipkgpu_db_file_close(h)
 
 
 def read_db(path, as_arrays=False, protocol=None):

@@ -306,6 +306,16 @@ class Engine:
 
 # ---- key-major parts / database shards (multi-GPU exchange step) ---------------------------------
 
+class DiffCounts(C.Structure):
+    """ipkgpu_db_diff_counts (include/ipkgpu.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("keys_a", "keys_b", "keys_only_a", "keys_only_b", "entries_a", "entries_b", "entries_only_a",
+                                          "entries_only_b", "scores_differ", "positions_differ")] + [("max_abs_diff", C.c_double)]
+
+
+# ipkgpu_db_diff_record: a difference of two databases; a score of NaN = not scored there
+DIFF_RECORD = np.dtype([("key", "<u4"), ("branch", "<u4"), ("a_score", "<f4"), ("b_score", "<f4")])
+
+
 def _bind_keymajor(L):
     if getattr(L, "_km_bound", False):
         return
@@ -417,6 +427,18 @@ def _bind_keymajor(L):
     L.ipkgpu_mem_stats.argtypes = [C.c_void_p, u64p, u64p, C.c_int]
     L.ipkgpu_get_option.restype = C.c_int
     L.ipkgpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+    L.ipkgpu_db_load.restype = C.c_int
+    L.ipkgpu_db_load.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_header_of.restype = C.c_void_p
+    L.ipkgpu_db_header_of.argtypes = [C.c_void_p]
+    L.ipkgpu_db_load_time.restype = C.c_double
+    L.ipkgpu_db_load_time.argtypes = [C.c_void_p, C.c_int]
+    L.ipkgpu_db_diff.restype = C.c_int
+    L.ipkgpu_db_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(DiffCounts), C.c_void_p, C.c_uint64, u64p]
+    L.ipkgpu_db_diff_time_ms.restype = C.c_double
+    L.ipkgpu_db_diff_time_ms.argtypes = [C.c_void_p]
+    L.ipkgpu_db_diff_chunk.restype = C.c_uint32
+    L.ipkgpu_db_diff_chunk.argtypes = []
     L._km_bound = True
 
 
@@ -439,6 +461,7 @@ ABI_SYMBOLS += [
     "ipkgpu_score_groups_keymajor_positions_owners_device", "ipkgpu_merge_parts_positions_ptrs",
     "ipkgpu_parts_spill", "ipkgpu_spill_merge", "ipkgpu_mem_stats", "ipkgpu_get_option",
     "ipkgpu_db_filter_random",
+    "ipkgpu_db_load", "ipkgpu_db_header_of", "ipkgpu_db_load_time", "ipkgpu_db_diff", "ipkgpu_db_diff_time_ms", "ipkgpu_db_diff_chunk",
 ]
 
 
@@ -500,6 +523,8 @@ class Parts:
 
 class Db:
     """One owner's shard of the phylo-k-mer database: key -> [(branch, score)] in reference order."""
+
+    header = None          # Engine.load_db: the head of the file the database was loaded from (dbfile.file_info's dict)
 
     def __init__(self, lib, handle):
         self._lib, self._h = lib, handle
@@ -858,3 +883,53 @@ Engine.get_option = _get_option
 Engine.parts_spill = _parts_spill
 Engine.spill_merge = _spill_merge
 Engine.mem_stats = _mem_stats
+
+
+def _load_db(self, path):
+    """ipkgpu_db_load: a database file onto the device -- the Db the builds produce, with the file's filter values and record order
+    (filter_values(), filter_order()) and `.header`, the dict dbfile.read_db returns for the file's head.
+    dbfile.write_db_device(engine, db, path, **dbfile.header_args(db.header)) gives the file back byte for byte."""
+    from . import dbfile
+    _bind_keymajor(self._lib)
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_db_load(self._h, os.fsencode(path), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    db = self._adopt(Db(self._lib, out))
+    db.header = dbfile.info_of_handle(self._lib.ipkgpu_db_header_of(out))
+    return db
+
+
+def _load_times(self):
+    """The engine's last load_db: seconds in all / reading the file / in the host's walk / waiting for the device, and milliseconds of
+    db_unpack_heads_kernel, db_unpack_entries_kernel and of all device work behind the last copy (ipkgpu_db_load_time)."""
+    _bind_keymajor(self._lib)
+    names = ("total_s", "read_s", "walk_s", "device_wait_s", "heads_ms", "entries_ms", "device_ms")
+    return {k: float(self._lib.ipkgpu_db_load_time(self._h, i)) for i, k in enumerate(names)}
+
+
+def _diff_dbs(self, a, b, eps=1e-2, max_records=0):
+    """ipkgpu_db_diff: the reference's ipkdiff comparison (tools/src/diff.cpp:210-295) of two databases of this engine on the device.
+    Returns (counts dict, records): records = the first max_records differences as a DIFF_RECORD array (ascending key; inside a key
+    A's entries in A's order, then B's unmatched ones in B's order; NaN = not scored).  eps = 0: the score bits must be equal."""
+    _bind_keymajor(self._lib)
+    counts = DiffCounts()
+    rec = np.zeros(max(int(max_records), 1), DIFF_RECORD)
+    n = C.c_uint64(0)
+    rc = self._lib.ipkgpu_db_diff(self._h, a._h, b._h, float(eps), C.byref(counts), rec.ctypes.data, int(max_records), C.byref(n))
+    if rc != 0:
+        raise self._err(rc)
+    d = {name: int(getattr(counts, name)) for name, _ in DiffCounts._fields_[:-1]}
+    d["max_abs_diff"] = float(counts.max_abs_diff)
+    return d, rec[:int(n.value)].copy()
+
+
+def _diff_time_ms(self):
+    _bind_keymajor(self._lib)
+    return float(self._lib.ipkgpu_db_diff_time_ms(self._h))
+
+
+Engine.load_db = _load_db
+Engine.load_times = _load_times
+Engine.diff_dbs = _diff_dbs
+Engine.diff_time_ms = _diff_time_ms
