@@ -12,54 +12,12 @@ import pytest
 from ipk_amd.synth import synth_matrices
 from oracle import ipk_oracle as co
 from tests import db_check as dc
+from tests.grid_paths import all_sums as _all_sums, classify, half as _half, split as _split
 
 pytestmark = pytest.mark.gpu
 SIGMA = 4
 CAP = 160                                    # half-list capacity of the k <= 10 kernels
 GROUPS = np.array([11, 11, 4, 4], dtype=np.uint32)
-
-
-def _split(k):
-    """(LA, LB, RA, RB): the window's halves (k // 2 | rest) and their children, each halved the same way."""
-    hl = k // 2
-    hr = k - hl
-    return hl // 2, hl - hl // 2, hr // 2, hr - hr // 2
-
-
-def _all_sums(cols):
-    """float64 scores of all 4^h h-mers over the h columns `cols`, first symbol most significant."""
-    s = np.zeros(1)
-    for c in cols:
-        s = (s[:, None] + c[None, :].astype(np.float64)).ravel()
-    return s
-
-
-def _half(cols, ha, hb, eps_h):
-    """One half of a window under its threshold eps_h: (first child's list length, second child's, half-list length)."""
-    ma, mb = cols[:ha].max(axis=1).astype(np.float64).sum(), cols[ha:].max(axis=1).astype(np.float64).sum()
-    a, b = _all_sums(cols[:ha]), _all_sums(cols[ha:])
-    a, b = a[a > eps_h - mb], b[b > eps_h - ma]                      # child lists: s > e - M(rest)
-    return len(a), len(b), int(((a[:, None] + b[None, :]) > eps_h).sum())
-
-
-def classify(mats, k, eps):
-    """Counts of windows per path, in float64 (close enough for counting)."""
-    la, lb, ra, rb = _split(k)
-    hl = la + lb
-    n = dict(single=0, one_long=0, both_long=0, one_row=0, over_cap=0, cap_lists=[])
-    for m in mats:
-        cmax = m.max(axis=1).astype(np.float64)
-        for w in range(m.shape[0] - k + 1):
-            win = m[w:w + k]
-            eps_l, eps_r = eps - cmax[w + hl:w + k].sum(), eps - cmax[w:w + hl].sum()   # s > eps - M(other half)
-            nla, nlb, nl = _half(win[:hl], la, lb, eps_l)
-            nra, nrb, nr = _half(win[hl:], ra, rb, eps_r)
-            long_l, long_r = nla * nlb > 64, nra * nrb > 64
-            n["single" if not (long_l or long_r) else "both_long" if long_l and long_r else "one_long"] += 1
-            n["one_row"] += (long_l and nlb > 32) or (long_r and nrb > 32)
-            n["over_cap"] += nl > CAP or nr > CAP
-            n["cap_lists"].append((nl, nr))
-    return n
 
 
 def _oracle(mats, groups, k, eps):
