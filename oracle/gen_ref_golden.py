@@ -112,6 +112,36 @@ def tenth_matrices(n_mats, sites, sigma, seed, rng=None):
     return np.ascontiguousarray(m, dtype=np.float32)
 
 
+def shifted_twins(m):
+    """Matrix n // 2 + i becomes matrix i one site further down (its first site stays its own), as in grid_matrices."""
+    half = len(m) // 2
+    for i in range(half):
+        m[half + i, 1:] = m[i, :-1]
+    return np.ascontiguousarray(m, dtype=np.float32)
+
+
+def tenth_twin_matrices(n_mats, sites, sigma, seed):
+    """tenth_matrices whose second half are the shifted twins of the first (shifted_twins)."""
+    return shifted_twins(tenth_matrices(n_mats, sites, sigma, seed))
+
+
+HEAVY = 1000                     # a heavy column's entries are float32(-0.1) * (HEAVY + 0..5): around -100
+
+
+def tenth_floor_matrices(n_mats, sites, sigma, seed, heavy=0, twins=True):
+    """float32 [n_mats, heavy + sites, sigma], "tenth with column floors": every entry float32(-0.1) * an integer, a column's
+    integers being a floor of 0..3 plus 0..5 a state -- so a column's maximum is rarely 0 even among 20 states, and the prefix
+    sums of the maxima behind the look-ahead bounds round at nearly every site.  `heavy` leading columns have integers around
+    HEAVY: they only enlarge the prefix sums (and so their rounding) under the windows behind them; a window that touches one
+    scores nothing at any threshold a test uses.  With `twins` the second half of the matrices are shifted twins (shifted_twins)."""
+    rng = np.random.default_rng(seed)
+    c = rng.integers(0, 4, size=(n_mats, heavy + sites, 1))
+    ints = c + rng.integers(0, 6, size=(n_mats, heavy + sites, sigma))
+    ints[:, :heavy] += HEAVY
+    m = (np.float32(-0.1) * ints.astype(np.float32)) + np.float32(0.0)
+    return shifted_twins(m) if twins else np.ascontiguousarray(m, dtype=np.float32)
+
+
 def dense_window_scores(m, k, start):
     """All sigma^k candidate scores of one window, indexed by key rank (first symbol most significant).  On grid inputs every
     sum is exact, so the association of the additions does not matter."""

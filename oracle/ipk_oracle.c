@@ -115,8 +115,17 @@ static vec_t as_column(const win_t* w, size_t j, float eps)
     return col;
 }
 
-/* DCLA::DC -- pk_compute.cpp:42-114 */
-static vec_t dc(const win_t* w, size_t j, size_t h, float eps)
+/* A deviation for tests, off by default (tests/rounded_paths.py compiles a second library with -DIPKO_DEVIATE_INNER_GE into a
+ * temporary directory): the joins below the top level keep a pair that scores exactly their node's bound.  The top-level join
+ * (`top`) stays strict.  With the macro undefined DROPS is the reference's `score <= eps` at every level. */
+#ifdef IPKO_DEVIATE_INNER_GE
+#define DROPS(score, eps, top) ((top) ? (score) <= (eps) : (score) < (eps))
+#else
+#define DROPS(score, eps, top) ((void)(top), (score) <= (eps))
+#endif
+
+/* DCLA::DC -- pk_compute.cpp:42-114 (`top`: the call for the whole window; only DROPS reads it) */
+static vec_t dc_node(const win_t* w, size_t j, size_t h, float eps, int top)
 {
     if (h == 1) return as_column(w, j, eps);
 
@@ -126,8 +135,8 @@ static vec_t dc(const win_t* w, size_t j, size_t h, float eps)
     const float eps_l = eps - range_max(w->best, w->start + j + hl, hr);
     const float eps_r = eps - range_max(w->best, w->start + j, hl);
 
-    vec_t l = dc(w, j, hl, eps_l);
-    vec_t r = dc(w, j + hl, hr, eps_r);
+    vec_t l = dc_node(w, j, hl, eps_l, 0);
+    vec_t r = dc_node(w, j + hl, hr, eps_r, 0);
 
     /* sort whichever side is smaller, pk_compute.cpp:61-70 */
     const int prefix_sort = l.n < r.n;
@@ -145,7 +154,7 @@ static vec_t dc(const win_t* w, size_t j, size_t h, float eps)
                 const uint32_t b = mn->v[i2].key; const float b_score = mn->v[i2].score;
                 if (b_score < eps_min) break;               /* :85-88 */
                 const float score = a_score + b_score;
-                if (score <= eps) break;                    /* :90-94 */
+                if (DROPS(score, eps, top)) break;          /* :90-94  score <= eps */
                 uint32_t kmer;                              /* :96-104 */
                 if (prefix_sort) kmer = (b << (hr * w->bits)) | a;
                 else             kmer = (a << (hr * w->bits)) | b;
@@ -156,6 +165,8 @@ static vec_t dc(const win_t* w, size_t j, size_t h, float eps)
     free(l.v); free(r.v);
     return result;
 }
+
+static vec_t dc(const win_t* w, size_t j, size_t h, float eps) { return dc_node(w, j, h, eps, 1); }
 
 /* One window: DCLA(window,k).run(eps); get_result()  -- pk_compute.cpp:28-38,116-119.
  * Returns the number of scored phylo-k-mers; writes at most cap of them. */
@@ -329,8 +340,8 @@ void ipko_window_halves(const float* m, const float* best, unsigned sigma, unsig
     const size_t hl = k / 2, hr = k - k / 2;
     const float eps_l = eps - range_max(best, start + hl, hr);
     const float eps_r = eps - range_max(best, start, hl);
-    vec_t l = dc(&w, 0, hl, eps_l);
-    vec_t r = dc(&w, hl, hr, eps_r);
+    vec_t l = dc_node(&w, 0, hl, eps_l, 0);
+    vec_t r = dc_node(&w, hl, hr, eps_r, 0);
     *nl = l.n; *nr = r.n;
     free(l.v); free(r.v);
 }

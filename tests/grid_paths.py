@@ -189,8 +189,12 @@ def matrices(case):
 
 @functools.lru_cache(maxsize=None)
 def load(name):
-    """(case, matrices, exact path counts), computed once."""
-    case = CASES.get(name) or {TENTH.name: TENTH}[name]
+    """(case, matrices, exact path counts), computed once; of a case of either table, this one (and TENTH) or tests/rounded_paths.py's
+    (whose sums round: no exact path counts)."""
+    case = CASES.get(name) or {TENTH.name: TENTH}.get(name)
+    if case is None:
+        from tests import rounded_paths
+        return rounded_paths.load(name) + (None,)
     mats = matrices(case)
     return case, mats, (path_counts(mats, case.sigma, case.k, case.eps) if case.family != "tenth" else None)
 

@@ -2,8 +2,9 @@
 the big-list kernels, the list slices and the second tiles of every kernel family with thousands of candidates exactly on a bound
 and thousands of keys whose score ties across windows, tiles and matrices, so a `>=` at the final join of any of these paths, or
 a tie broken for the later window, changes a key set, a scored count or a position here.  (A `>=` at an inner half join does not: on
-exact sums a half-list candidate exactly on its bound never passes the final join.  There the tenth-valued case decides, whose bounds
-round: with `>=` in half_join_rows it scores 545 716 k-mers instead of 545 574.)  Expected values come from the oracle, pinned on these very
+exact sums a half-list candidate exactly on its bound never passes the final join.  There inputs whose bounds round decide: the
+tenth-valued case below -- with `>=` in half_join_rows it scores 545 716 k-mers instead of 545 574 -- and, for every kernel family,
+tests/test_gpu_rounded_paths.py, which reuses the checkers of this file by case name.)  Expected values come from the oracle, pinned on these very
 cases by tests/test_grid_paths_inputs.py; every comparison is exact (key sets, raw score bits, positions, scored counts) through
 tests/db_check.py.  Every test first asserts, through the CPU classifier, that its case still reaches its paths.  The engine fixture
 is shared by the session: every test restores the options it sets."""
@@ -18,6 +19,7 @@ from ipk_amd import keyrange
 from tests import db_check as dc
 from tests import grid_paths as gp
 from tests import long_lists as ll
+from tests import rounded_paths as rp
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +37,10 @@ POOL_LIMIT = {"dna_k10": 32 << 20, "dna_k12": 16 << 20}
 def on_its_paths(name):
     """The case with its paths asserted: (case, matrices, exact path counts).  A case that has drifted fails here, before the engine runs."""
     case, mats, counts = gp.load(name)
+    if name in rp.CASES:                                 # sums round: the recorded counts come from the oracle's own list building
+        counts = rp.cheap_counts(name)
+        assert counts == {key: rp.COUNTS[name][key] for key in counts}, f"{name}: the recorded counts moved: {counts}"
+        return case, mats, counts
     if case.family == "tenth":
         over = sum(max(nl, nr) > 160 for _, _, nl, nr in ll.longest_half_lists(mats, case.k, case.eps))
         assert over >= gp.TENTH_OVER_CAP, f"{name}: only {over} windows with a half list beyond 160"
@@ -203,8 +209,15 @@ def test_key_range_passes(engine, name):
     """DNA k = 15 as tests/test_gpu_long_lists.py::test_key_range_passes walks it: every class of the first symbol against its range
     of the oracle's database, the scored counts summed; the right halves beyond the cap are sliced."""
     case, mats, counts = on_its_paths(name)
+    assert case.k == 15 and int((gp.half_lists(mats, case.k, case.eps)[:, 1] > gp.BIG_CAP).sum()) >= 3
+    assert check_key_range(engine, name) > 0
+
+
+def check_key_range(engine, name):
+    """Every key-range pass of a DNA k = 15 / 16 case against its range of the oracle's database; returns the windows sliced."""
+    case, mats, counts = on_its_paths(name)
     k, lead = case.k, case.k - 14
-    assert lead == 1 and int((gp.half_lists(mats, k, case.eps)[:, 1] > gp.BIG_CAP).sum()) >= 3
+    assert lead >= 1
     ok, ooff, obr, osc, _ = gp.oracle_db(name)
     ooff = ooff.astype(np.int64)
     total, seen = 0, 0
@@ -222,8 +235,9 @@ def test_key_range_passes(engine, name):
             assert np.array_equal(br, obr[ooff[a]:ooff[b]]) and np.array_equal(sc.view(np.uint32), osc[ooff[a]:ooff[b]])
             seen += len(keys)
             db.free(); parts.free()
-        assert sliced() > 0
+        n_sliced = sliced()
     assert seen == len(ok) and total == expected(name)[1]
+    return n_sliced
 
 
 # ---- stress modes ----------------------------------------------------------------------------------------------------------------

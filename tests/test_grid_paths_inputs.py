@@ -10,6 +10,7 @@ from oracle import ipk_oracle as co
 from oracle import ref_build as rb
 from tests import grid_paths as gp
 from tests import long_lists as ll
+from tests import rounded_paths as rp
 
 needs_binaries = pytest.mark.skipif(not rb.available(), reason="the reference binaries are not in oracle/_ref/ "
                                     "(oracle.ref_build.build() found no reference tree and none were carried along)")
@@ -107,8 +108,10 @@ def test_first_two_windows_against_dense_enumeration(name):
 
 
 @needs_binaries
-@pytest.mark.parametrize("name", NAMES + [gp.TENTH.name])
+@pytest.mark.parametrize("name", NAMES + [gp.TENTH.name] + list(rp.CASES))
 def test_oracle_against_the_live_reference(name):
+    """Also on every case of tests/rounded_paths.py: where the bounds round, the oracle's restated sort and break logic could itself
+    differ from the reference's."""
     case, mats, _ = gp.load(name)
     per_matrix = rb.ref_windows_many(mats, case.k, case.eps, case.sigma)
     for gid, keys, bits, pos, emitted in gp.oracle(name):
