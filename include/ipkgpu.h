@@ -115,7 +115,9 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * point: per-branch result, key-major with and without owners or positions, key-range passes, ipkgpu_score_groups_positions, the
  * pieces of the on-disk build; results of calls without such a window do not change);
  * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "db_load_chunk_bytes" (bytes of each of the two pinned buffers a file passes
- * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "release_workspaces" (any value: the context's workspaces and cached result
+ * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
+ * "place_lds_branches" (0..4096: the branch count up to which ipkgpu_db_place keeps a query's sums in LDS; 0 = 4096; tests lower it to reach
+ * the global tables with small inputs); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
  * Every variant yields identical results.  Returns IPKGPU_ERR_INVALID for unknown names.
  *
@@ -603,6 +605,47 @@ int ipkgpu_db_diff(ipkgpu_ctx* ctx, const ipkgpu_db* a, const ipkgpu_db* b, doub
 double ipkgpu_db_diff_time_ms(const ipkgpu_ctx* ctx);
 /* DB_DIFF_CHUNK: the entries of a list the general path of ipkgpu_db_diff keeps in LDS at a time (tests build a longer list). */
 uint32_t ipkgpu_db_diff_chunk(void);
+
+/* ---- placement: the k-mers of query sequences looked up in a database on the device ---------------------------------------
+ * What every consumer of a phylo-k-mer database does with it.  For a database of alphabet sigma and k-mer size k, the threshold
+ * log_eps (ipkgpu_log_threshold of the database's omega) and a query q of n bytes:
+ *   symbols    the database's code order (DNA ACGT, 2 bits; AA RHKDESTNQCGPAILMFWYV, 5 bits), either letter case, DNA U = T; every
+ *              other byte (N, X, *, -, . included) is invalid
+ *   windows    start s (0 <= s <= n - k) is valid iff its k bytes are; its code packs them, first symbol in the highest bits; W = the
+ *              number of valid windows, every occurrence of a k-mer counting
+ *   sums       S[b] = +0.0f, C[b] = 0; the valid windows in ASCENDING s: where the code is a key, for each of its entries (b, x)
+ *              S[b] = S[b] + x in binary32 and C[b] += 1 -- a branch's scores are added in window order, as a sequential loop adds them
+ *   score      for C[b] > 0: score[b] = S[b] + ((float)(W - C[b]) * log_eps), product and sum each rounded to binary32
+ *   placements the branches with C[b] > 0 by score descending, then branch id ascending; the first keep_at_most of them
+ *   lwr        (binary64) m = the best score, den = the sum of 10^((double)score[b] - (double)m) over ALL branches with C[b] > 0 (in any
+ *              order), lwr[b] = 10^(score[b] - m) / den
+ * Precondition: a key's entries name a branch at most once (every build of this library; checked on a database's first placement
+ * call, IPKGPU_ERR_INVALID naming the key).  That first call also builds the database's prefix table (at most 2^16 + 1 lower bounds
+ * into the key list) and finds the branch count; both stay with the database until ipkgpu_db_free.
+ *   seqs, seq_off   host arrays: query i is bytes [seq_off[i], seq_off[i + 1]) of seqs
+ * The queries go to the device in batches (option "place_batch_queries"; 0 = sized from what the device or "device_budget_bytes"
+ * leaves), one wavefront per query (kernels_place.hpp); S and C live in LDS while the database has at most "place_lds_branches"
+ * branches (0 = the default and the most, 4096), else in global tables -- the same bits either way.
+ * IPKGPU_ERR_INVALID: sigma / k that are not the database's (codes of more than 32 bits, a key beyond sigma's k symbols, the head of
+ * the file a database was loaded from), keep_at_most outside 1..64, a decreasing seq_off, a query of 2^32 bytes or more.
+ * IPKGPU_ERR_NOMEM leaves the context usable.  Not done here: reverse complements, expansion of ambiguous symbols, jplace output. */
+typedef struct ipkgpu_placements ipkgpu_placements;
+int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, float log_eps, const char* seqs, const uint64_t* seq_off,
+                    uint64_t n_queries, uint32_t keep_at_most, ipkgpu_placements** out);
+uint64_t ipkgpu_placements_num_queries(const ipkgpu_placements* p);
+uint32_t ipkgpu_placements_keep(const ipkgpu_placements* p);
+/* [num_queries][keep], best first; past a query's last placement: branch 0xFFFFFFFF, score 0, count 0, lwr 0 */
+const uint32_t* ipkgpu_placements_branches(const ipkgpu_placements* p);
+const float* ipkgpu_placements_scores(const ipkgpu_placements* p);
+const uint32_t* ipkgpu_placements_counts(const ipkgpu_placements* p);    /* C[b]: the query's windows that scored the branch */
+const double* ipkgpu_placements_lwr(const ipkgpu_placements* p);
+/* [num_queries]: valid windows (W), those whose code is a key, branches with C > 0 */
+const uint32_t* ipkgpu_placements_n_kmers(const ipkgpu_placements* p);
+const uint32_t* ipkgpu_placements_n_found(const ipkgpu_placements* p);
+const uint32_t* ipkgpu_placements_n_branches(const ipkgpu_placements* p);
+/* milliseconds: 0 = the whole call on the host's clock, 1 = the index build (0 when the database had it), 2 = the placement kernels */
+double ipkgpu_placements_time_ms(const ipkgpu_placements* p, int which);
+void ipkgpu_placements_free(ipkgpu_placements* p);
 
 #ifdef __cplusplus
 }

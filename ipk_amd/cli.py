@@ -15,6 +15,7 @@ Alignment reduction/extension and RUNNING the ancestral reconstruction are IPK's
   ipk.py build -r aln.fasta -t tree.nwk -w work --ar-dir work/AR -k 10
   ipk.py diff [-v] [--eps 1e-2 | --exact] A.ipk B.ipk          (the reference's ipkdiff; exit status 1 on a difference)
   ipk.py dump [--limit N] DB.ipk                               (the reference's ipkdump)
+  ipk.py place -i DB.ipk -q reads.fasta [-o out.tsv]            (this engine's: the reads' k-mers looked up and summed per branch)
 
 --mapping (optional, not in the reference): TSV `ar_node_label <TAB> branch_postorder_id` per ghost node in scoring order;
 replaces the tree-derived plan (synthetic inputs without trees).
@@ -402,6 +403,72 @@ def dump(limit, device, db):
                 node = pre[b] if pre is not None and b < len(pre) else b
                 out.append(f"\t{_g(10.0 ** float(sc[j]))}\t{node}" + (f"\t{int(pos[j])}" if pos is not None else ""))
         click.echo("\n".join(out))
+        d.free()
+    finally:
+        eng.close()
+
+
+# ---- placement: what a database is for ---------------------------------------------------------------------------------------------
+
+def read_fasta(text):
+    """[(name, sequence)] of FASTA text: records may span lines, the name is the header's text up to the first blank, and '-', '.' and
+    whitespace are dropped from the sequence.  Lines before the first header are ignored."""
+    out = []
+    for line in text.splitlines():
+        if line.startswith(">"):
+            words = line[1:].split()
+            out.append((words[0] if words else "", []))
+        elif out:
+            out[-1][1].append("".join(ch for ch in line if not ch.isspace() and ch not in "-."))
+    return [(name, "".join(parts)) for name, parts in out]
+
+
+def placement_lines(names, res, keep_factor):
+    """The TSV lines of `ipk.py place` for a Placements: per query its placements best first while lwr >= keep_factor x the best's
+    lwr -- query, branch, score (%.9g: the float's bits), count, n_kmers, lwr (%.17g); a query without placements: one line of '-'."""
+    from ipk_amd.engine import PLACE_NONE
+    lines = []
+    for i, name in enumerate(names):
+        kept = 0
+        for j in range(res.keep):
+            if int(res.branches[i, j]) == PLACE_NONE or res.lwr[i, j] < keep_factor * res.lwr[i, 0]:
+                break
+            lines.append(f"{name}\t{int(res.branches[i, j])}\t{float(res.scores[i, j]):.9g}\t{int(res.counts[i, j])}\t{int(res.n_kmers[i])}\t"
+                         f"{float(res.lwr[i, j]):.17g}")
+            kept += 1
+        if kept == 0:
+            lines.append(f"{name}\t-\t-\t-\t{int(res.n_kmers[i])}\t-")
+    return lines
+
+
+@ipk.command()
+@click.option("-i", "--input", "db_path", required=True, type=click.Path(exists=True, dir_okay=False), help="database file (of this engine's builds)")
+@click.option("-q", "--queries", required=True, type=click.Path(exists=True, dir_okay=False), help="query sequences (FASTA)")
+@click.option("-o", "--output", default=None, help="output TSV [standard output]")
+@click.option("--keep-at-most", type=click.IntRange(1, 64), default=7, show_default=True, help="placements kept per query at most")
+@click.option("--keep-factor", type=float, default=0.01, show_default=True, help="a placement is kept while its lwr >= this x the best one's")
+@click.option("--device", type=int, default=0, show_default=True, help="GPU index")
+def place(db_path, queries, output, keep_at_most, keep_factor, device):
+    """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
+    branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
+
+    One TSV line per kept placement: query, branch, score, count, n_kmers, lwr -- branch is the stored post-order id (what `dump`
+    prints for a file without a tree), score the log10 score with the threshold standing in for the query's k-mers the branch does
+    not score, count those it does, n_kmers the query's valid k-mers.  The given strand only; symbols outside the alphabet (N, X, ...)
+    end a k-mer, they are not expanded."""
+    import ipk_amd
+    with open(queries) as fh:
+        recs = read_fasta(fh.read())
+    eng = ipk_amd.Engine(device)
+    try:
+        d = eng.load_db(db_path)
+        res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most)
+        text = "".join(line + "\n" for line in placement_lines([n for n, _ in recs], res, keep_factor))
+        if output:
+            with open(output, "w") as fh:
+                fh.write(text)
+        else:
+            click.echo(text, nl=False)
         d.free()
     finally:
         eng.close()

@@ -43,6 +43,7 @@
 #include "kernels_spill.hpp"
 #include "kernels_dbload.hpp"
 #include "kernels_dbdiff.hpp"
+#include "kernels_place.hpp"
 #include "db_file.hpp"
 #include "spill_format.hpp"
 #include <sys/stat.h>
@@ -173,6 +174,10 @@ struct ipkgpu_ctx {
     int64_t opt_load_chunk = 0;          // "db_load_chunk_bytes": bytes per pinned buffer of ipkgpu_db_load (0: SPILL_STAGE, the spill blocks')
     double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
     double t_diff_ms = 0;
+    // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters
+    DevBuf place_seq, place_off, place_out, place_tables, place_small;
+    int64_t opt_place_batch = 0;         // "place_batch_queries": queries per batch (0: by the budget)
+    int64_t opt_place_lds = 0;           // "place_lds_branches": branch count up to which S and C stay in LDS (0: PLACE_LDS_BRANCHES, also the most)
     int num_cu = 256;
 };
 
@@ -236,6 +241,11 @@ struct ipkgpu_db {
     bool h_filter_ok = false;
     double t_filter = 0;
     ipkgpu_db_file* file = nullptr;           // ipkgpu_db_load: the head of the file the database came from (owned)
+    // ipkgpu_db_place: built on the first placement call (db_place.hpp) -- the prefix table over the keys' high bits, for codes of
+    // place_bits bits; place_branches = 1 + the largest branch id
+    uint32_t* d_place_index = nullptr;
+    uint32_t place_bits = 0, place_shift = 0, place_slots = 0, place_branches = 0;
+    double t_place_index = 0;
 };
 
 static std::string g_create_err;
@@ -409,7 +419,8 @@ static std::vector<DevBuf*> all_workspaces(ipkgpu_ctx* ctx)
             &ctx->pool, &ctx->desc, &ctx->gbcnt, &ctx->gboff, &ctx->gbcur, &ctx->clist, &ctx->gm, &ctx->tile_next, &ctx->mask,
             &ctx->rank, &ctx->vaddr, &ctx->ucnt, &ctx->qpack, &ctx->xstart, &ctx->pcounts, &ctx->ptrs,
             &ctx->cvals, &ctx->coff, &ctx->croom, &ctx->seq, &ctx->pvals, &ctx->pvaddr, &ctx->mrank, &ctx->cursnap,
-            &ctx->sp_bits, &ctx->sp_pops, &ctx->sp_rank, &ctx->sp_c16};
+            &ctx->sp_bits, &ctx->sp_pops, &ctx->sp_rank, &ctx->sp_c16,
+            &ctx->place_seq, &ctx->place_off, &ctx->place_out, &ctx->place_tables, &ctx->place_small};
 }
 
 extern "C" {
@@ -518,6 +529,17 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
     if (!strcmp(name, "db_load_chunk_bytes")) {
         if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "db_load_chunk_bytes must not be negative (0 = the default)");
         ctx->opt_load_chunk = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "place_batch_queries")) {
+        if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "place_batch_queries must not be negative (0 = by the budget)");
+        ctx->opt_place_batch = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "place_lds_branches")) {
+        if (value < 0 || value > (int64_t)PLACE_LDS_BRANCHES)
+            return fail(ctx, IPKGPU_ERR_INVALID, "place_lds_branches is 0 (the default, %u) .. %u", PLACE_LDS_BRANCHES, PLACE_LDS_BRANCHES);
+        ctx->opt_place_lds = value;
         return IPKGPU_OK;
     }
     if (!strcmp(name, "variant")) { ctx->opt_variant = value; return IPKGPU_OK; }
@@ -2867,6 +2889,7 @@ void ipkgpu_db_free(ipkgpu_db* d)
         ctx_release(d->ctx, d->d_keys); ctx_release(d->ctx, d->d_key_off); ctx_release(d->ctx, d->d_entries);
         ctx_release(d->ctx, d->d_positions);
         ctx_release(d->ctx, d->d_fv64); ctx_release(d->ctx, d->d_fv32); ctx_release(d->ctx, d->d_order);
+        ctx_release(d->ctx, d->d_place_index);
     }
     ipkgpu_db_file_close(d->file);
     delete d;
@@ -3169,6 +3192,8 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
     if (!strcmp(name, "slice_long_lists")) { *value = ctx->opt_slice; return IPKGPU_OK; }
     if (!strcmp(name, "db_load_chunk_bytes")) { *value = ctx->opt_load_chunk; return IPKGPU_OK; }
+    if (!strcmp(name, "place_batch_queries")) { *value = ctx->opt_place_batch; return IPKGPU_OK; }
+    if (!strcmp(name, "place_lds_branches")) { *value = ctx->opt_place_lds; return IPKGPU_OK; }
     if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
     if (!strcmp(name, "debug_pool_bytes")) { *value = (int64_t)ctx->pool.cap; return IPKGPU_OK; }   // bytes the pair pool holds (tests)
     return IPKGPU_ERR_INVALID;
@@ -3388,4 +3413,5 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 }  // extern "C"
 
 #include "db_load.hpp"
+#include "db_place.hpp"
 #include "comm_rccl.hpp"

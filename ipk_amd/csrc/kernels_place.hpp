@@ -1,0 +1,293 @@
+// kernels_place.hpp -- places query sequences on a database that lives on the device (ipkgpu_db_place; DESIGN.md section 3, "Placement").
+//
+// The definition (include/ipkgpu.h): every valid window of a query is a k-mer code; the codes that are keys of the database add
+// their entries' scores to S[branch] IN WINDOW ORDER, in binary32, and 1 to C[branch]; score[b] = S[b] + (float)(W - C[b]) * log_eps
+// over the W valid windows; the best `keep` branches by (score descending, branch ascending) and their likelihood weight ratios.
+//
+//   place_index_kernel     once per database: lower bounds into keys[] of the 2^P prefixes of the code (P = min(16, code bits)), so a
+//                          lookup is a binary search inside one prefix's short range
+//   place_max_branch_kernel, place_dupcheck_kernel   once per database: B = 1 + the largest branch id, and the precondition that
+//                          a key names a branch once (a bitmap per wavefront in LDS, PLACE_DUP_BITS branches per pass)
+//   place_kernel           one wavefront per query.  64 windows at a time: the lanes' symbols become bit planes (one ballot per bit of
+//                          the symbol code and one for "valid symbol"), a lane's window code and validity are shifts of those planes --
+//                          no lane reads a symbol twice; every lane looks its window up.  Then the 64 windows are walked in order, the
+//                          lanes taking a window's entries 64 at a time (branches are distinct inside a key: no conflicts, no atomics),
+//                          the next tile's entries loaded under the current tile's adds: one branch's scores are added in window
+//                          order by construction.  S, C and the list of touched branches live in LDS up to PLACE_LDS_BRANCHES
+//                          branches (template parameter GLOBAL = false), beyond that in the workgroup's slice of a global scratch
+//                          block (GLOBAL = true); the address space is fixed per instantiation, never a generic pointer.
+//                          Epilogue: over the touched branches only -- scores, a sorted top list of one 64-bit (score, branch) word
+//                          per lane, the f64 denominator; the same walk clears S and C for the workgroup's next query.
+#pragma once
+#include "../../include/ipkgpu.h"
+#include "dcla_device.hpp"
+
+namespace ipkgpu {
+
+constexpr uint32_t PLACE_INDEX_BITS = 16;        // the prefix table has at most 2^16 + 1 lower bounds
+// S (f32), C (u32) and the touched list (u32) of a query stay in LDS up to this many branches: 12 bytes each, 48 KiB of the CU's
+// 160 KiB at the bound (three queries per CU there); the launch sizes the block's LDS by the database's own branch count, so a tree of a
+// few hundred branches leaves the CU to the wavefront limit.  Trees beyond the bound use the global tables.
+constexpr uint32_t PLACE_LDS_BRANCHES = 4096;
+constexpr uint32_t PLACE_DUP_BITS = 32768;       // branches per pass of the per-wavefront bitmap of place_dupcheck_kernel (4 KiB)
+constexpr uint32_t PLACE_NONE = 0xFFFFFFFFu;     // "no placement" in the branch array
+constexpr uint32_t PLACE_SYMTAB_BYTES = 256;
+
+// code of a sequence byte in the database's symbol order (DNA ACGT, U = T; AA RHKDESTNQCGPAILMFWYV), case-insensitive; 0xFF: invalid
+__device__ __forceinline__ uint32_t place_symbol(uint32_t sigma, uint32_t byte)
+{
+    const uint32_t c = (byte >= 'a' && byte <= 'z') ? byte - 32u : byte;
+    if (sigma == 4) {
+        switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': case 'U': return 3; default: return 0xFF; }
+    }
+    switch (c) {
+    case 'R': return 0; case 'H': return 1; case 'K': return 2; case 'D': return 3; case 'E': return 4; case 'S': return 5; case 'T': return 6;
+    case 'N': return 7; case 'Q': return 8; case 'C': return 9; case 'G': return 10; case 'P': return 11; case 'A': return 12; case 'I': return 13;
+    case 'L': return 14; case 'M': return 15; case 'F': return 16; case 'W': return 17; case 'Y': return 18; case 'V': return 19;
+    default: return 0xFF;
+    }
+}
+
+// table[j] = the number of keys below j << shift, j = 0 .. n_slots (table[n_slots] = n_keys)
+__global__ __launch_bounds__(256) void place_index_kernel(const uint32_t* __restrict__ keys, uint32_t n_keys, uint32_t shift, uint32_t n_slots,
+                                                          uint32_t* __restrict__ table)
+{
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j > n_slots) return;
+    uint32_t lo = 0, hi = n_keys;
+    if (j == n_slots) lo = n_keys;
+    else {
+        const uint32_t key = j << shift;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (keys[mid] < key) lo = mid + 1; else hi = mid;
+        }
+    }
+    table[j] = lo;
+}
+
+__global__ __launch_bounds__(256) void place_max_branch_kernel(const uint2* __restrict__ entries, uint64_t n_entries, uint32_t* __restrict__ max_branch)
+{
+    uint32_t m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_entries; i += (uint64_t)gridDim.x * 256) m = max(m, entries[i].x);
+    for (int s = 32; s > 0; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+    if (lane_id() == 0) atomicMax(max_branch, m);
+}
+
+// One wavefront per key (keys [first, ...)): *bad_key = the lowest index of a key whose entries name a branch twice.
+__global__ __launch_bounds__(256) void place_dupcheck_kernel(const uint64_t* __restrict__ key_off, const uint2* __restrict__ entries, uint64_t n_keys,
+                                                             uint32_t n_branches, uint64_t first, unsigned long long* __restrict__ bad_key)
+{
+    __shared__ uint32_t bits[4][PLACE_DUP_BITS / 32];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = lane_id();
+    uint32_t* bm = bits[wave];
+    for (uint32_t t = lane; t < PLACE_DUP_BITS / 32; t += 64) bm[t] = 0;
+    wave_lds_sync();
+    const uint64_t i = first + (uint64_t)blockIdx.x * 4 + wave;
+    if (i >= n_keys) return;
+    const uint64_t a0 = key_off[i], n = key_off[i + 1] - a0;
+    if (n < 2) return;
+    bool dup = false;
+    for (uint32_t r0 = 0; r0 < n_branches; r0 += PLACE_DUP_BITS) {
+        for (uint64_t t0 = 0; t0 < n; t0 += 64) {
+            const uint32_t rel = (t0 + lane < n ? entries[a0 + t0 + lane].x : PLACE_NONE) - r0;
+            if (t0 + lane < n && rel < PLACE_DUP_BITS) {
+                const uint32_t old = atomicOr(&bm[rel >> 5], 1u << (rel & 31));
+                dup |= (old >> (rel & 31)) & 1u;
+            }
+        }
+        wave_lds_sync();
+        for (uint64_t t0 = 0; t0 < n; t0 += 64) {                        // the words this key touched, back to zero
+            const uint32_t rel = (t0 + lane < n ? entries[a0 + t0 + lane].x : PLACE_NONE) - r0;
+            if (t0 + lane < n && rel < PLACE_DUP_BITS) bm[rel >> 5] = 0;
+        }
+        wave_lds_sync();
+    }
+    if (ballot64(dup) != 0 && lane == 0) atomicMin(bad_key, (unsigned long long)i);
+}
+
+struct PlaceArgs {
+    // the database and its prefix table
+    const uint32_t* keys; const uint64_t* key_off; const uint2* entries; const uint32_t* index;
+    uint32_t shift, k, sigma, n_branches, b_pad;
+    float log_eps;
+    // the batch: query q is bytes [seq_off[q] - seq_base, seq_off[q + 1] - seq_base) of seqs
+    const unsigned char* seqs; const uint64_t* seq_off; uint64_t seq_base; uint32_t n_queries, keep;
+    // GLOBAL: [gridDim.x][b_pad] each, S and C zero on entry (and left zero)
+    float* g_s; uint32_t* g_c; uint32_t* g_touched;
+    // results of the batch: [n_queries][keep] and [n_queries]
+    uint32_t* out_branch; float* out_score; uint32_t* out_count; double* out_lwr; uint32_t* out_n_kmers; uint32_t* out_n_found; uint32_t* out_n_branches;
+};
+
+__device__ __forceinline__ uint64_t place_readlane64(uint64_t v, uint32_t l)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l);
+    return ((uint64_t)hi << 32) | lo;
+}
+// bits [lane, lane + 32) of the 128-bit plane (hi : lo)
+__device__ __forceinline__ uint32_t place_plane_at(uint64_t lo, uint64_t hi, uint32_t lane)
+{
+    return (uint32_t)(lane ? (lo >> lane) | (hi << (64 - lane)) : lo);
+}
+// (score, branch) as one word: a larger word is a better placement (higher score; on equal scores the lower branch id); never 0
+__device__ __forceinline__ uint64_t place_rank_word(float score, uint32_t branch)
+{
+    return ((uint64_t)enc_score_bits(__float_as_uint(score)) << 32) | (uint64_t)(0xFFFFFFFFu - branch);
+}
+
+template <int BITS, bool GLOBAL>
+__global__ __launch_bounds__(64) void place_kernel(PlaceArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char place_lds[];
+    unsigned char* symtab = place_lds;
+    float* S; uint32_t* C; uint32_t* touched;
+    if constexpr (GLOBAL) {
+        S = a.g_s + (size_t)blockIdx.x * a.b_pad; C = a.g_c + (size_t)blockIdx.x * a.b_pad; touched = a.g_touched + (size_t)blockIdx.x * a.b_pad;
+    } else {
+        S = reinterpret_cast<float*>(place_lds + PLACE_SYMTAB_BYTES);
+        C = reinterpret_cast<uint32_t*>(S + a.b_pad);
+        touched = C + a.b_pad;
+    }
+    const uint32_t lane = lane_id();
+    for (uint32_t t = lane; t < 256; t += 64) symtab[t] = (unsigned char)place_symbol(a.sigma, t);
+    if constexpr (!GLOBAL)
+        for (uint32_t t = lane; t < a.b_pad; t += 64) { S[t] = 0.0f; C[t] = 0; }
+    wave_lds_sync();
+    const uint32_t k = a.k, mask_k = (1u << k) - 1u;
+
+    for (uint32_t q = blockIdx.x; q < a.n_queries; q += gridDim.x) {
+        const uint64_t q0 = a.seq_off[q] - a.seq_base;
+        const uint32_t n = (uint32_t)(a.seq_off[q + 1] - a.seq_base - q0);
+        const unsigned char* seq = a.seqs + q0;
+        uint32_t W = 0, n_found = 0, n_touched = 0;
+
+        for (uint64_t base = 0; base + k <= n; base += 64) {
+            // ---- phase one: the codes of windows base .. base + 63 out of bit planes, and their lookup
+            const uint64_t p0 = base + lane, p1 = base + 64 + lane;
+            const uint32_t s_lo = p0 < n ? symtab[seq[p0]] : 0xFFu;
+            const uint32_t s_hi = (lane + 1 < k && p1 < n) ? symtab[seq[p1]] : 0xFFu;
+            const uint32_t valid_bits = place_plane_at(ballot64(s_lo != 0xFFu), ballot64(s_hi != 0xFFu), lane);
+            const bool win = (valid_bits & mask_k) == mask_k;            // (a window that runs past the end meets an invalid symbol there)
+            uint32_t plane[BITS];
+#pragma unroll
+            for (int p = 0; p < BITS; ++p) plane[p] = place_plane_at(ballot64((s_lo >> p) & 1u), ballot64((s_hi >> p) & 1u), lane);
+            uint32_t code = 0;
+            for (uint32_t i = 0; i < k; ++i) {
+                uint32_t sym = 0;
+#pragma unroll
+                for (int p = 0; p < BITS; ++p) sym |= ((plane[p] >> i) & 1u) << p;
+                code = (code << BITS) | sym;
+            }
+            uint64_t off = 0;
+            uint32_t cnt = 0;
+            bool found = false;
+            if (win) {
+                const uint32_t j = code >> a.shift;
+                uint32_t lo = a.index[j];
+                const uint32_t end = a.index[j + 1];
+                uint32_t hi = end;
+                while (lo < hi) {
+                    const uint32_t mid = lo + (hi - lo) / 2;
+                    if (a.keys[mid] < code) lo = mid + 1; else hi = mid;
+                }
+                if (lo < end && a.keys[lo] == code) {
+                    found = true;
+                    off = a.key_off[lo];
+                    cnt = (uint32_t)(a.key_off[lo + 1] - off);
+                }
+            }
+            W += (uint32_t)__popcll(ballot64(win));
+            n_found += (uint32_t)__popcll(ballot64(found));
+
+            // ---- phase two: the windows in order, a window's entries 64 at a time, the next tile loaded under this tile's adds
+            uint64_t todo = ballot64(cnt != 0);
+            uint64_t t_off = 0;
+            uint32_t t_cnt = 0, t_at = 0;
+            auto fetch = [&](uint2& e, bool& v) -> bool {
+                if (t_at >= t_cnt) {
+                    if (todo == 0) return false;
+                    const uint32_t w = (uint32_t)__builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    t_off = place_readlane64(off, w);
+                    t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cnt, (int)w);
+                    t_at = 0;
+                }
+                v = t_at + lane < t_cnt;
+                e = v ? a.entries[t_off + t_at + lane] : make_uint2(0, 0);
+                t_at += 64;
+                return true;
+            };
+            uint2 cur; bool cur_v;
+            bool more = fetch(cur, cur_v);
+            while (more) {
+                uint2 nxt = make_uint2(0, 0); bool nxt_v = false;
+                more = fetch(nxt, nxt_v);
+                bool fresh = false;
+                if (cur_v) {
+                    S[cur.x] = S[cur.x] + __uint_as_float(cur.y);
+                    const uint32_t c = C[cur.x];
+                    C[cur.x] = c + 1;
+                    fresh = c == 0;
+                }
+                const uint64_t fm = ballot64(fresh);
+                if (fresh) touched[n_touched + mbcnt(fm)] = cur.x;
+                n_touched += (uint32_t)__popcll(fm);
+                wave_lds_sync();                                          // (the next tile may name these branches from other lanes)
+                cur = nxt; cur_v = nxt_v;
+            }
+        }
+
+        // ---- epilogue: scores of the touched branches, the best `keep` of them sorted across the lanes (lane r = rank r)
+        uint64_t top = 0;
+        uint64_t kth = 0;                                                 // the word at rank keep - 1: what a candidate has to beat
+        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
+            const bool v = i0 + lane < n_touched;
+            uint64_t word = 0;
+            if (v) {
+                const uint32_t b = touched[i0 + lane];
+                const float pen = (float)(W - C[b]) * a.log_eps;
+                word = place_rank_word(S[b] + pen, b);
+            }
+            uint64_t pend = ballot64(word > kth);
+            while (pend) {
+                const uint32_t src = (uint32_t)__builtin_ctzll(pend);
+                pend &= pend - 1;
+                const uint64_t w = place_readlane64(word, src);
+                if (w <= kth) continue;
+                const uint64_t prev = __shfl_up((unsigned long long)top, 1, 64);
+                if (w > top) top = (lane > 0 && w > prev) ? prev : w;
+                kth = place_readlane64(top, a.keep - 1);
+            }
+        }
+        const uint32_t my_branch = top ? 0xFFFFFFFFu - (uint32_t)top : PLACE_NONE;
+        const float my_score = top ? __uint_as_float(dec_score_bits((uint32_t)(top >> 32))) : 0.0f;
+        const uint32_t my_count = top ? C[my_branch] : 0;
+        const float best = __uint_as_float(dec_score_bits((uint32_t)(place_readlane64(top, 0) >> 32)));
+        wave_lds_sync();
+        // the denominator over ALL touched branches (f64, any order); S and C back to zero for the next query
+        double den = 0.0;
+        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
+            if (i0 + lane < n_touched) {
+                const uint32_t b = touched[i0 + lane];
+                const float pen = (float)(W - C[b]) * a.log_eps;
+                const float score = S[b] + pen;
+                den += exp10((double)score - (double)best);
+                S[b] = 0.0f; C[b] = 0;
+            }
+        }
+        for (int s = 32; s > 0; s >>= 1) den += __shfl_xor(den, s, 64);
+        wave_lds_sync();
+        if (lane < a.keep) {
+            const size_t o = (size_t)q * a.keep + lane;
+            a.out_branch[o] = my_branch;
+            a.out_score[o] = my_score;
+            a.out_count[o] = my_count;
+            a.out_lwr[o] = top ? exp10((double)my_score - (double)best) / den : 0.0;
+        }
+        if (lane == 0) { a.out_n_kmers[q] = W; a.out_n_found[q] = n_found; a.out_n_branches[q] = n_touched; }
+    }
+}
+
+}  // namespace ipkgpu

@@ -933,3 +933,99 @@ Engine.load_db = _load_db
 Engine.load_times = _load_times
 Engine.diff_dbs = _diff_dbs
 Engine.diff_time_ms = _diff_time_ms
+
+
+# ---- placement: query sequences on a database of this engine (ipkgpu_db_place) ------------------------------------------------
+
+ABI_SYMBOLS += [
+    "ipkgpu_db_place", "ipkgpu_placements_num_queries", "ipkgpu_placements_keep", "ipkgpu_placements_branches",
+    "ipkgpu_placements_scores", "ipkgpu_placements_counts", "ipkgpu_placements_lwr", "ipkgpu_placements_n_kmers",
+    "ipkgpu_placements_n_found", "ipkgpu_placements_n_branches", "ipkgpu_placements_time_ms", "ipkgpu_placements_free",
+]
+
+PLACE_NONE = 0xFFFFFFFF      # the branch past a query's last placement
+
+
+def _bind_place(L):
+    if getattr(L, "_place_bound", False):
+        return
+    L.ipkgpu_db_place.restype = C.c_int
+    L.ipkgpu_db_place.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_placements_num_queries.restype = C.c_uint64
+    L.ipkgpu_placements_keep.restype = C.c_uint32
+    for name, t in (("branches", C.c_uint32), ("scores", C.c_float), ("counts", C.c_uint32), ("lwr", C.c_double), ("n_kmers", C.c_uint32),
+                    ("n_found", C.c_uint32), ("n_branches", C.c_uint32)):
+        getattr(L, "ipkgpu_placements_" + name).restype = C.POINTER(t)
+    for name in ("num_queries", "keep", "branches", "scores", "counts", "lwr", "n_kmers", "n_found", "n_branches", "free"):
+        getattr(L, "ipkgpu_placements_" + name).argtypes = [C.c_void_p]
+    L.ipkgpu_placements_time_ms.restype = C.c_double
+    L.ipkgpu_placements_time_ms.argtypes = [C.c_void_p, C.c_int]
+    L.ipkgpu_placements_free.restype = None
+    L._place_bound = True
+
+
+class Placements:
+    """Host arrays of one Engine.place call: branches u32 / scores f32 / counts u32 / lwr f64, each [n, keep] and best first (past a
+    query's last placement: branch PLACE_NONE, zeros); n_kmers / n_found / n_branches u32 [n]; time_ms: total (host clock), index
+    (the database's first call only) and place (the placement kernels)."""
+
+    def __init__(self, lib, h):
+        n, keep = int(lib.ipkgpu_placements_num_queries(h)), int(lib.ipkgpu_placements_keep(h))
+        self.n, self.keep = n, keep
+
+        def arr(name, dtype, shape):
+            if n == 0:
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(getattr(lib, "ipkgpu_placements_" + name)(h), shape=shape).astype(dtype, copy=True)
+        self.branches = arr("branches", np.uint32, (n, keep))
+        self.scores = arr("scores", np.float32, (n, keep))
+        self.counts = arr("counts", np.uint32, (n, keep))
+        self.lwr = arr("lwr", np.float64, (n, keep))
+        self.n_kmers = arr("n_kmers", np.uint32, (n,))
+        self.n_found = arr("n_found", np.uint32, (n,))
+        self.n_branches = arr("n_branches", np.uint32, (n,))
+        self.time_ms = {k: float(lib.ipkgpu_placements_time_ms(h, i)) for i, k in enumerate(("total", "index", "place"))}
+
+
+def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, log_eps=None):
+    """Engine.place over packed queries: `blob` (bytes or a uint8 array) holds query i at [offsets[i], offsets[i + 1])."""
+    _bind_keymajor(self._lib)
+    _bind_place(self._lib)
+    h = db.header
+    if sigma is None or k is None or log_eps is None:
+        if h is None:
+            raise ValueError("sigma, k and log_eps are needed for a database that was not loaded from a file")
+        sigma = {"DNA": 4, "AA": 20}.get(h["sequence_type"], 0) if sigma is None else sigma
+        k = h["kmer_size"] if k is None else k
+        log_eps = log_threshold(h["omega"], sigma, k) if log_eps is None else log_eps
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(off) < 1:
+        raise ValueError("offsets needs one element more than there are queries")
+    data = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+    if len(off) > 1 and int(off.max()) > len(data):
+        raise ValueError("an offset points past the end of the sequences")
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_db_place(self._h, db._h, int(sigma), int(k), C.c_float(log_eps), data.ctypes.data, off.ctypes.data, len(off) - 1,
+                                   int(keep_at_most), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    try:
+        return Placements(self._lib, out)
+    finally:
+        self._lib.ipkgpu_placements_free(out)
+
+
+def _place(self, db, seqs, keep_at_most=7, sigma=None, k=None, log_eps=None):
+    """ipkgpu_db_place: places the query sequences `seqs` (str or bytes each) on the database `db` of this engine -> Placements.
+    sigma, k and log_eps default to those of the file a loaded database came from (its header's sequence type, k-mer size and
+    log_threshold(omega, sigma, k)); a database built in this process needs them given."""
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    off = np.zeros(len(raw) + 1, np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return _place_packed(self, db, b"".join(raw), off, keep_at_most, sigma, k, log_eps)
+
+
+Engine.place_packed = _place_packed
+Engine.place = _place
