@@ -140,12 +140,16 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
     uint32_t slices = 0;
     for (uint64_t q0 = 0; q0 < n_queries;) {
         // the batch: as many queries as the option or the budget allows (a first query always: what it needs is then asked for and may be refused)
-        const uint64_t room = mem_free_bytes(ctx) / 2 + ctx->place_seq.cap + ctx->place_off.cap + ctx->place_out.cap;
+        // A workspace is no room for another: each is counted by what it would have to grow by, as ensure grows it (the old block
+        // freed first, a sixteenth on top of what is asked for), and the three together take at most half of what is free.
+        const uint64_t room = mem_free_bytes(ctx) / 2;
         const uint64_t most = ctx->opt_place_batch > 0 ? (uint64_t)ctx->opt_place_batch : PLACE_BATCH_QUERIES;
+        auto grows = [](const DevBuf& b, uint64_t need) -> uint64_t { return need <= b.cap ? 0 : need + need / 16 - b.cap; };
         uint64_t q1 = q0 + 1;
         while (q1 < n_queries && q1 - q0 < most) {
-            const uint64_t bytes = seq_off[q1 + 1] - seq_off[q0];
-            if (bytes > PLACE_BATCH_BYTES || bytes + (q1 + 1 - q0) * per_query > room) break;
+            const uint64_t bytes = seq_off[q1 + 1] - seq_off[q0], n = q1 + 1 - q0;
+            if (bytes > PLACE_BATCH_BYTES ||
+                grows(ctx->place_seq, bytes + 16) + grows(ctx->place_off, (n + 1) * 8) + grows(ctx->place_out, n * per_query + 64) > room) break;
             ++q1;
         }
         const uint64_t nq = q1 - q0, bytes = seq_off[q1] - seq_off[q0];

@@ -216,6 +216,7 @@ class Engine:
         if rc != 0:
             raise IpkGpuError(rc, self._lib.ipkgpu_last_error(None).decode())
         self._h = h
+        self.device_id = device_id
 
     def _err(self, rc):
         return IpkGpuError(rc, self._lib.ipkgpu_last_error(self._h).decode())
