@@ -628,7 +628,8 @@ uint32_t ipkgpu_db_diff_chunk(void);
  * branches (0 = the default and the most, 4096), else in global tables -- the same bits either way.
  * IPKGPU_ERR_INVALID: sigma / k that are not the database's (codes of more than 32 bits, a key beyond sigma's k symbols, the head of
  * the file a database was loaded from), keep_at_most outside 1..64, a decreasing seq_off, a query of 2^32 bytes or more.
- * IPKGPU_ERR_NOMEM leaves the context usable.  Not done here: reverse complements, expansion of ambiguous symbols, jplace output. */
+ * IPKGPU_ERR_NOMEM leaves the context usable.  ipkgpu_db_place places the strand given and treats ambiguous symbols as invalid bytes;
+ * ipkgpu_db_place_opts (below) expands them and places both strands.  Not done here: jplace output. */
 typedef struct ipkgpu_placements ipkgpu_placements;
 int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, float log_eps, const char* seqs, const uint64_t* seq_off,
                     uint64_t n_queries, uint32_t keep_at_most, ipkgpu_placements** out);
@@ -646,6 +647,47 @@ const uint32_t* ipkgpu_placements_n_branches(const ipkgpu_placements* p);
 /* milliseconds: 0 = the whole call on the host's clock, 1 = the index build (0 when the database had it), 2 = the placement kernels */
 double ipkgpu_placements_time_ms(const ipkgpu_placements* p, int which);
 void ipkgpu_placements_free(ipkgpu_placements* p);
+
+/* ---- placement with options: ambiguous symbols expanded, both strands placed ----------------------------------------------
+ * opts == NULL or {0, 0}: ipkgpu_db_place's result bit for bit (the same kernels), strand and n_ambiguous all zero.  Any other value
+ * of either field, and strands = 1 with sigma = 20: IPKGPU_ERR_INVALID.  Every refusal of ipkgpu_db_place and its IPKGPU_ERR_NOMEM
+ * contract carry over.
+ *
+ * ambiguity = 1.  Ambiguous symbols, either letter case, and their resolutions:
+ *   DNA          R = AG   Y = CT   S = CG   W = AT   K = GT   M = AC   B = CGT   D = AGT   H = ACT   V = ACG   N = ACGT
+ *   amino acids  B = DN   Z = EQ   J = IL   X = all 20
+ * every other byte stays invalid.  A window is EXACT if its k bytes are plain symbols, AMBIGUOUS if k - 1 are plain and exactly one
+ * is an ambiguous symbol, invalid otherwise.  W counts exact and ambiguous windows, n_ambiguous the ambiguous ones.  An ambiguous
+ * window has R resolutions: its code with the ambiguous position replaced by each resolution, in ascending symbol code.  If any
+ * resolution is a key, n_found grows by 1.  For every branch b named by at least one resolution's key, c = the number of resolutions
+ * that name it:
+ *     P = 0.0;  for the resolutions in ascending order that name b with score x:  P = P + 10^(double)x          (binary64)
+ *     P = P + (double)(R - c) * E        E = 10^(double)log_eps, product and sum each rounded to binary64
+ *     y = (float)log10(P / (double)R)    one rounding to binary32
+ *     S[b] = S[b] + y;  C[b] += 1        at the window's own place in the ascending order of starts
+ * -- the mean of the resolutions' probabilities, the threshold standing in for the resolutions that do not score the branch.  A
+ * branch that no resolution names gets nothing from the window (the (W - C[b]) log_eps term covers it as it covers any window).
+ * This definition is this library's own: it follows what the placement tools that read such databases do with a window of one
+ * ambiguous symbol, and was not checked against their code.
+ * 10^x and log10 are not the same functions bit for bit in every implementation: two implementations of this definition can differ
+ * in the last bit of y where the binary64 value of log10(P / R) lies within their error of a binary32 rounding midpoint.
+ *
+ * strands = 1 (DNA only).  rc(q) is q reversed with A <-> T (U -> A), C <-> G, R <-> Y, K <-> M, B <-> V, D <-> H; S, W and N map to
+ * themselves, every other byte stays as it is (an invalid byte stays invalid).  q and rc(q) are each placed by the whole
+ * definition, independently.  The reverse strand is the query's result iff it has a placement and either the given strand has none
+ * or its best score is greater (as floats); equal scores go to the given strand.  Every output of the query comes from the chosen
+ * strand; strand[i] says which.
+ * The device reads rc(q) out of the uploaded bytes of q; the per-window tables of ambiguous windows (16 bytes per branch and
+ * workgroup) live in device memory and count against "device_budget_bytes" like the batch's other workspaces. */
+typedef struct ipkgpu_place_options {
+    uint32_t ambiguity;   /* 0: an ambiguous symbol is an invalid byte (ipkgpu_db_place). 1: expanded, above */
+    uint32_t strands;     /* 0: the strand given. 1: both strands, DNA only */
+} ipkgpu_place_options;
+int ipkgpu_db_place_opts(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, float log_eps, const char* seqs,
+                         const uint64_t* seq_off, uint64_t n_queries, uint32_t keep_at_most, const ipkgpu_place_options* opts,
+                         ipkgpu_placements** out);
+const uint8_t* ipkgpu_placements_strand(const ipkgpu_placements* p);        /* [num_queries] 0 = given, 1 = reverse complement */
+const uint32_t* ipkgpu_placements_n_ambiguous(const ipkgpu_placements* p);  /* [num_queries] expanded (ambiguous) windows */
 
 #ifdef __cplusplus
 }

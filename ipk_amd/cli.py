@@ -423,21 +423,23 @@ def read_fasta(text):
     return [(name, "".join(parts)) for name, parts in out]
 
 
-def placement_lines(names, res, keep_factor):
+def placement_lines(names, res, keep_factor, with_strand=False):
     """The TSV lines of `ipk.py place` for a Placements: per query its placements best first while lwr >= keep_factor x the best's
-    lwr -- query, branch, score (%.9g: the float's bits), count, n_kmers, lwr (%.17g); a query without placements: one line of '-'."""
+    lwr -- query, branch, score (%.9g: the float's bits), count, n_kmers, lwr (%.17g); a query without placements: one line of '-'.
+    with_strand: a seventh column, '+' (the strand given) or '-' (its reverse complement was placed)."""
     from ipk_amd.engine import PLACE_NONE
     lines = []
+    tail = (lambda i: "\t-" if res.strand[i] else "\t+") if with_strand else (lambda i: "")
     for i, name in enumerate(names):
         kept = 0
         for j in range(res.keep):
             if int(res.branches[i, j]) == PLACE_NONE or res.lwr[i, j] < keep_factor * res.lwr[i, 0]:
                 break
             lines.append(f"{name}\t{int(res.branches[i, j])}\t{float(res.scores[i, j]):.9g}\t{int(res.counts[i, j])}\t{int(res.n_kmers[i])}\t"
-                         f"{float(res.lwr[i, j]):.17g}")
+                         f"{float(res.lwr[i, j]):.17g}" + tail(i))
             kept += 1
         if kept == 0:
-            lines.append(f"{name}\t-\t-\t-\t{int(res.n_kmers[i])}\t-")
+            lines.append(f"{name}\t-\t-\t-\t{int(res.n_kmers[i])}\t-" + tail(i))
     return lines
 
 
@@ -447,23 +449,27 @@ def placement_lines(names, res, keep_factor):
 @click.option("-o", "--output", default=None, help="output TSV [standard output]")
 @click.option("--keep-at-most", type=click.IntRange(1, 64), default=7, show_default=True, help="placements kept per query at most")
 @click.option("--keep-factor", type=float, default=0.01, show_default=True, help="a placement is kept while its lwr >= this x the best one's")
+@click.option("--expand-ambiguous", is_flag=True, default=False,
+              help="expand a k-mer with one ambiguous symbol (N, R, Y, ...; amino acids B, Z, J, X) into its resolutions")
+@click.option("--strands", type=click.Choice(["given", "both"]), default="given", show_default=True,
+              help="both: place the reverse complement too (DNA) and keep the better strand; adds a seventh column, + or -")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def place(db_path, queries, output, keep_at_most, keep_factor, device):
+def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, device):
     """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
     branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
 
     One TSV line per kept placement: query, branch, score, count, n_kmers, lwr -- branch is the stored post-order id (what `dump`
     prints for a file without a tree), score the log10 score with the threshold standing in for the query's k-mers the branch does
-    not score, count those it does, n_kmers the query's valid k-mers.  The given strand only; symbols outside the alphabet (N, X, ...)
-    end a k-mer, they are not expanded."""
+    not score, count those it does, n_kmers the query's valid k-mers.  By default the given strand only, and symbols outside the
+    alphabet (N, X, ...) end a k-mer; --expand-ambiguous and --strands both change that (ipkgpu_db_place_opts in include/ipkgpu.h)."""
     import ipk_amd
     with open(queries) as fh:
         recs = read_fasta(fh.read())
     eng = ipk_amd.Engine(device)
     try:
         d = eng.load_db(db_path)
-        res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most)
-        text = "".join(line + "\n" for line in placement_lines([n for n, _ in recs], res, keep_factor))
+        res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
+        text = "".join(line + "\n" for line in placement_lines([n for n, _ in recs], res, keep_factor, strands == "both"))
         if output:
             with open(output, "w") as fh:
                 fh.write(text)

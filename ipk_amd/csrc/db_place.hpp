@@ -1,5 +1,7 @@
 // db_place.hpp -- ipkgpu_db_place: query sequences placed on a database of this context (included by ipkgpu.hip; kernels_place.hpp).
 //
+// ipkgpu_db_place_opts is the same call with ambiguous symbols expanded and / or both strands placed (place_ext_kernel); without
+// options it launches what ipkgpu_db_place always launched.
 // First call on a database: the prefix table over the keys' high bits, B = 1 + the largest branch id, and the check that no key names
 // a branch twice (the kernels add a key's entries without atomics) -- cached in the database, freed with it.  Every call: the queries
 // go to the device in batches sized from what the budget leaves, one wavefront places one query, the small results come back.
@@ -8,7 +10,8 @@
 struct ipkgpu_placements {
     uint64_t n = 0;
     uint32_t keep = 0;
-    std::vector<uint32_t> branches, counts, n_kmers, n_found, n_branches;
+    std::vector<uint32_t> branches, counts, n_kmers, n_found, n_branches, n_ambiguous;
+    std::vector<uint8_t> strand;
     std::vector<float> scores;
     std::vector<double> lwr;
     double t_index = 0, t_place = 0, t_total = 0;
@@ -19,8 +22,8 @@ namespace {
 constexpr uint64_t PLACE_BATCH_QUERIES = 1ull << 18;      // most queries of an automatic batch, PLACE_BATCH_BYTES: most sequence bytes
 constexpr uint64_t PLACE_BATCH_BYTES = 256ull << 20;
 
-// device bytes of a batch's results and offsets per query
-inline uint64_t place_query_bytes(uint32_t keep) { return 8 + (uint64_t)keep * (8 + 4 + 4 + 4) + 3 * 4; }
+// device bytes of a batch's results and offsets per query (ext: strand and n_ambiguous as well)
+inline uint64_t place_query_bytes(uint32_t keep, bool ext) { return 8 + (uint64_t)keep * (8 + 4 + 4 + 4) + 3 * 4 + (ext ? 2 * 4 : 0); }
 
 // The database's placement index for codes of `bits` bits (sigma, k of the call): built once, kept in the database.
 int place_prepare(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t bits)
@@ -75,8 +78,20 @@ int place_prepare(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t bits)
     return IPKGPU_OK;
 }
 
-int place_launch(ipkgpu_ctx* ctx, const PlaceArgs& a, uint32_t bits_per_symbol, bool global, uint32_t grid)
+int place_launch(ipkgpu_ctx* ctx, const PlaceArgs& a, const PlaceExtArgs* x, uint32_t bits_per_symbol, bool global, uint32_t grid)
 {
+    if (x) {
+        const size_t lds = PLACE_EXT_TAB_BYTES + (global ? 0 : (size_t)a.b_pad * 12);
+        if (bits_per_symbol == 2) {
+            if (global) hipLaunchKernelGGL((place_ext_kernel<2, true>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
+            else hipLaunchKernelGGL((place_ext_kernel<2, false>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
+        } else {
+            if (global) hipLaunchKernelGGL((place_ext_kernel<5, true>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
+            else hipLaunchKernelGGL((place_ext_kernel<5, false>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        return IPKGPU_OK;
+    }
     const size_t lds = PLACE_SYMTAB_BYTES + (global ? 0 : (size_t)a.b_pad * 12);
     if (bits_per_symbol == 2) {
         if (global) hipLaunchKernelGGL((place_kernel<2, true>), dim3(grid), dim3(64), lds, ctx->stream, a);
@@ -96,9 +111,19 @@ extern "C" {
 int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, float log_eps, const char* seqs, const uint64_t* seq_off,
                     uint64_t n_queries, uint32_t keep_at_most, ipkgpu_placements** out)
 {
+    return ipkgpu_db_place_opts(ctx, db, sigma, k, log_eps, seqs, seq_off, n_queries, keep_at_most, nullptr, out);
+}
+
+int ipkgpu_db_place_opts(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, float log_eps, const char* seqs, const uint64_t* seq_off,
+                         uint64_t n_queries, uint32_t keep_at_most, const ipkgpu_place_options* opts, ipkgpu_placements** out)
+{
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (out) *out = nullptr;
     if (!db || db->ctx != ctx || !out) return fail(ctx, IPKGPU_ERR_INVALID, "bad argument");
+    const uint32_t ambiguity = opts ? opts->ambiguity : 0, strands = opts ? opts->strands : 0;
+    if (ambiguity > 1 || strands > 1) return fail(ctx, IPKGPU_ERR_INVALID, "place options: ambiguity and strands are 0 or 1 each");
+    if (strands && sigma != 4) return fail(ctx, IPKGPU_ERR_INVALID, "both strands are placed for DNA only (sigma = 4)");
+    const bool ext = ambiguity || strands;
     if (n_queries && (!seq_off || (!seqs && seq_off[n_queries] != seq_off[0]))) return fail(ctx, IPKGPU_ERR_INVALID, "null sequence arrays");
     const uint32_t bps = ipkgpu_bits_per_symbol(sigma);
     if (bps == 0 || k < 1 || k > 16 || bps * k > 32)
@@ -129,12 +154,20 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
         res->branches.resize(n_queries * keep); res->counts.resize(n_queries * keep); res->scores.resize(n_queries * keep);
         res->lwr.resize(n_queries * keep);
         res->n_kmers.resize(n_queries); res->n_found.resize(n_queries); res->n_branches.resize(n_queries);
+        res->n_ambiguous.assign(n_queries, 0); res->strand.assign(n_queries, 0);
     } catch (const std::bad_alloc&) { return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory"); }
 
     const uint32_t B = db->place_branches, b_pad = std::max<uint32_t>((B + 63) & ~63u, 64);
     const uint32_t lds_bound = ctx->opt_place_lds > 0 ? (uint32_t)ctx->opt_place_lds : PLACE_LDS_BRANCHES;
     const bool global = B > lds_bound;
-    const uint64_t per_query = place_query_bytes(keep);
+    const uint64_t per_query = place_query_bytes(keep, ext);
+    const uint32_t max_grid = (uint32_t)ctx->num_cu * (global ? 4 : 32);
+    const uint64_t amb_slice_bytes = (uint64_t)b_pad * 16;                 // P (f64), c and the window's touched list per workgroup
+    PlaceExtArgs x;
+    x.ambiguity = ambiguity; x.strands = strands; x.E = std::pow(10.0, (double)log_eps);
+    x.g_p = nullptr; x.g_wc = nullptr; x.g_wtouched = nullptr;
+    std::vector<uint32_t> h_strand;
+    uint32_t amb_slices = 0;
     Stopwatch sw(ctx->stream, &ctx->events);
     std::vector<std::pair<int, int>> marks;
     uint32_t slices = 0;
@@ -148,15 +181,17 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
         uint64_t q1 = q0 + 1;
         while (q1 < n_queries && q1 - q0 < most) {
             const uint64_t bytes = seq_off[q1 + 1] - seq_off[q0], n = q1 + 1 - q0;
+            // (ambiguity: the per-window tables of the workgroups that n queries start)
+            const uint64_t amb_grows = ambiguity ? grows(ctx->place_amb, std::min<uint64_t>(n, max_grid) * amb_slice_bytes) : 0;
             if (bytes > PLACE_BATCH_BYTES ||
-                grows(ctx->place_seq, bytes + 16) + grows(ctx->place_off, (n + 1) * 8) + grows(ctx->place_out, n * per_query + 64) > room) break;
+                grows(ctx->place_seq, bytes + 16) + grows(ctx->place_off, (n + 1) * 8) + grows(ctx->place_out, n * per_query + 64) + amb_grows > room) break;
             ++q1;
         }
         const uint64_t nq = q1 - q0, bytes = seq_off[q1] - seq_off[q0];
         RC_TRY(ensure(ctx, ctx->place_seq, bytes + 16));
         RC_TRY(ensure(ctx, ctx->place_off, (nq + 1) * 8));
         RC_TRY(ensure(ctx, ctx->place_out, nq * per_query + 64));
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, (uint64_t)ctx->num_cu * (global ? 4 : 32));
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, max_grid);
         if (global && grid > slices) {
             // a slice of S, C and the touched list per workgroup; S and C zero before the first launch, and every launch leaves them so
             uint32_t want = grid;
@@ -166,6 +201,15 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
             RC_TRY(ensure(ctx, ctx->place_tables, (uint64_t)want * slice_bytes));
             HIP_TRY(ctx, hipMemsetAsync(ctx->place_tables.p, 0, (uint64_t)want * b_pad * 8, ctx->stream));
             slices = want;
+        }
+        if (ambiguity && grid > amb_slices) {
+            // the same for P, c and the window's touched list: P and c zero before the first launch, and every launch leaves them so
+            uint32_t want = grid;
+            if ((uint64_t)want * amb_slice_bytes > ctx->place_amb.cap)
+                want = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (mem_free_bytes(ctx) / 2 + ctx->place_amb.cap) / amb_slice_bytes));
+            RC_TRY(ensure(ctx, ctx->place_amb, (uint64_t)want * amb_slice_bytes));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->place_amb.p, 0, (uint64_t)want * b_pad * 12, ctx->stream));
+            amb_slices = want;
         }
         if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->place_seq.p, seqs + seq_off[q0], bytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->place_off.p, seq_off + q0, (nq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -184,9 +228,20 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
         a.out_count = reinterpret_cast<uint32_t*>(o); o += nq * keep * 4;
         a.out_n_kmers = reinterpret_cast<uint32_t*>(o); o += nq * 4;
         a.out_n_found = reinterpret_cast<uint32_t*>(o); o += nq * 4;
-        a.out_n_branches = reinterpret_cast<uint32_t*>(o);
+        a.out_n_branches = reinterpret_cast<uint32_t*>(o); o += nq * 4;
+        uint32_t launch_grid = global ? std::min(grid, slices) : grid;
+        if (ext) {
+            x.out_strand = reinterpret_cast<uint32_t*>(o); o += nq * 4;
+            x.out_n_ambiguous = reinterpret_cast<uint32_t*>(o);
+            if (ambiguity) {
+                x.g_p = ctx->place_amb.as<double>();
+                x.g_wc = ctx->place_amb.as<uint32_t>() + (size_t)2 * amb_slices * b_pad;
+                x.g_wtouched = ctx->place_amb.as<uint32_t>() + (size_t)3 * amb_slices * b_pad;
+                launch_grid = std::min(launch_grid, amb_slices);
+            }
+        }
         const int m0 = sw.mark();
-        RC_TRY(place_launch(ctx, a, bps, global, global ? std::min(grid, slices) : grid));
+        RC_TRY(place_launch(ctx, a, ext ? &x : nullptr, bps, global, launch_grid));
         marks.push_back({m0, sw.mark()});
         HIP_TRY(ctx, hipMemcpyAsync(res->lwr.data() + q0 * keep, a.out_lwr, nq * keep * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(res->branches.data() + q0 * keep, a.out_branch, nq * keep * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -195,7 +250,13 @@ int ipkgpu_db_place(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_t k, 
         HIP_TRY(ctx, hipMemcpyAsync(res->n_kmers.data() + q0, a.out_n_kmers, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(res->n_found.data() + q0, a.out_n_found, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(res->n_branches.data() + q0, a.out_n_branches, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (ext) {
+            try { h_strand.resize(nq); } catch (const std::bad_alloc&) { return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory"); }
+            HIP_TRY(ctx, hipMemcpyAsync(h_strand.data(), x.out_strand, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(res->n_ambiguous.data() + q0, x.out_n_ambiguous, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                 // (the buffers serve the next batch)
+        if (ext) for (uint64_t i = 0; i < nq; ++i) res->strand[q0 + i] = (uint8_t)h_strand[i];
         q0 = q1;
     }
     for (const auto& m : marks) res->t_place += sw.ms(m.first, m.second);
@@ -213,6 +274,8 @@ const double* ipkgpu_placements_lwr(const ipkgpu_placements* p) { return p ? p->
 const uint32_t* ipkgpu_placements_n_kmers(const ipkgpu_placements* p) { return p ? p->n_kmers.data() : nullptr; }
 const uint32_t* ipkgpu_placements_n_found(const ipkgpu_placements* p) { return p ? p->n_found.data() : nullptr; }
 const uint32_t* ipkgpu_placements_n_branches(const ipkgpu_placements* p) { return p ? p->n_branches.data() : nullptr; }
+const uint8_t* ipkgpu_placements_strand(const ipkgpu_placements* p) { return p ? p->strand.data() : nullptr; }
+const uint32_t* ipkgpu_placements_n_ambiguous(const ipkgpu_placements* p) { return p ? p->n_ambiguous.data() : nullptr; }
 double ipkgpu_placements_time_ms(const ipkgpu_placements* p, int which)
 {
     if (!p) return 0;

@@ -174,8 +174,9 @@ struct ipkgpu_ctx {
     int64_t opt_load_chunk = 0;          // "db_load_chunk_bytes": bytes per pinned buffer of ipkgpu_db_load (0: SPILL_STAGE, the spill blocks')
     double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
     double t_diff_ms = 0;
-    // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters
-    DevBuf place_seq, place_off, place_out, place_tables, place_small;
+    // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
+    // place_amb: the per-window tables of ambiguous windows (ipkgpu_db_place_opts)
+    DevBuf place_seq, place_off, place_out, place_tables, place_small, place_amb;
     int64_t opt_place_batch = 0;         // "place_batch_queries": queries per batch (0: by the budget)
     int64_t opt_place_lds = 0;           // "place_lds_branches": branch count up to which S and C stay in LDS (0: PLACE_LDS_BRANCHES, also the most)
     int num_cu = 256;
@@ -420,7 +421,7 @@ static std::vector<DevBuf*> all_workspaces(ipkgpu_ctx* ctx)
             &ctx->rank, &ctx->vaddr, &ctx->ucnt, &ctx->qpack, &ctx->xstart, &ctx->pcounts, &ctx->ptrs,
             &ctx->cvals, &ctx->coff, &ctx->croom, &ctx->seq, &ctx->pvals, &ctx->pvaddr, &ctx->mrank, &ctx->cursnap,
             &ctx->sp_bits, &ctx->sp_pops, &ctx->sp_rank, &ctx->sp_c16,
-            &ctx->place_seq, &ctx->place_off, &ctx->place_out, &ctx->place_tables, &ctx->place_small};
+            &ctx->place_seq, &ctx->place_off, &ctx->place_out, &ctx->place_tables, &ctx->place_small, &ctx->place_amb};
 }
 
 extern "C" {

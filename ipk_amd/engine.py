@@ -942,9 +942,14 @@ ABI_SYMBOLS += [
     "ipkgpu_db_place", "ipkgpu_placements_num_queries", "ipkgpu_placements_keep", "ipkgpu_placements_branches",
     "ipkgpu_placements_scores", "ipkgpu_placements_counts", "ipkgpu_placements_lwr", "ipkgpu_placements_n_kmers",
     "ipkgpu_placements_n_found", "ipkgpu_placements_n_branches", "ipkgpu_placements_time_ms", "ipkgpu_placements_free",
+    "ipkgpu_db_place_opts", "ipkgpu_placements_strand", "ipkgpu_placements_n_ambiguous",
 ]
 
 PLACE_NONE = 0xFFFFFFFF      # the branch past a query's last placement
+
+
+class _PlaceOptions(C.Structure):
+    _fields_ = [("ambiguity", C.c_uint32), ("strands", C.c_uint32)]
 
 
 def _bind_place(L):
@@ -953,12 +958,15 @@ def _bind_place(L):
     L.ipkgpu_db_place.restype = C.c_int
     L.ipkgpu_db_place.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64,
                                   C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_place_opts.restype = C.c_int
+    L.ipkgpu_db_place_opts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_uint32, C.POINTER(_PlaceOptions), C.POINTER(C.c_void_p)]
     L.ipkgpu_placements_num_queries.restype = C.c_uint64
     L.ipkgpu_placements_keep.restype = C.c_uint32
     for name, t in (("branches", C.c_uint32), ("scores", C.c_float), ("counts", C.c_uint32), ("lwr", C.c_double), ("n_kmers", C.c_uint32),
-                    ("n_found", C.c_uint32), ("n_branches", C.c_uint32)):
+                    ("n_found", C.c_uint32), ("n_branches", C.c_uint32), ("strand", C.c_uint8), ("n_ambiguous", C.c_uint32)):
         getattr(L, "ipkgpu_placements_" + name).restype = C.POINTER(t)
-    for name in ("num_queries", "keep", "branches", "scores", "counts", "lwr", "n_kmers", "n_found", "n_branches", "free"):
+    for name in ("num_queries", "keep", "branches", "scores", "counts", "lwr", "n_kmers", "n_found", "n_branches", "strand", "n_ambiguous", "free"):
         getattr(L, "ipkgpu_placements_" + name).argtypes = [C.c_void_p]
     L.ipkgpu_placements_time_ms.restype = C.c_double
     L.ipkgpu_placements_time_ms.argtypes = [C.c_void_p, C.c_int]
@@ -968,8 +976,9 @@ def _bind_place(L):
 
 class Placements:
     """Host arrays of one Engine.place call: branches u32 / scores f32 / counts u32 / lwr f64, each [n, keep] and best first (past a
-    query's last placement: branch PLACE_NONE, zeros); n_kmers / n_found / n_branches u32 [n]; time_ms: total (host clock), index
-    (the database's first call only) and place (the placement kernels)."""
+    query's last placement: branch PLACE_NONE, zeros); n_kmers / n_found / n_branches u32 [n]; strand u8 [n] (0: the strand given,
+    1: the reverse complement was placed) and n_ambiguous u32 [n] (expanded windows), both zero without the options of Engine.place;
+    time_ms: total (host clock), index (the database's first call only) and place (the placement kernels)."""
 
     def __init__(self, lib, h):
         n, keep = int(lib.ipkgpu_placements_num_queries(h)), int(lib.ipkgpu_placements_keep(h))
@@ -986,11 +995,15 @@ class Placements:
         self.n_kmers = arr("n_kmers", np.uint32, (n,))
         self.n_found = arr("n_found", np.uint32, (n,))
         self.n_branches = arr("n_branches", np.uint32, (n,))
+        self.strand = arr("strand", np.uint8, (n,))
+        self.n_ambiguous = arr("n_ambiguous", np.uint32, (n,))
         self.time_ms = {k: float(lib.ipkgpu_placements_time_ms(h, i)) for i, k in enumerate(("total", "index", "place"))}
 
 
-def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, log_eps=None):
+def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, log_eps=None, ambiguity=False, strands="given"):
     """Engine.place over packed queries: `blob` (bytes or a uint8 array) holds query i at [offsets[i], offsets[i + 1])."""
+    if strands not in ("given", "both"):
+        raise ValueError('strands is "given" or "both"')
     _bind_keymajor(self._lib)
     _bind_place(self._lib)
     h = db.header
@@ -1007,8 +1020,13 @@ def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, l
     if len(off) > 1 and int(off.max()) > len(data):
         raise ValueError("an offset points past the end of the sequences")
     out = C.c_void_p()
-    rc = self._lib.ipkgpu_db_place(self._h, db._h, int(sigma), int(k), C.c_float(log_eps), data.ctypes.data, off.ctypes.data, len(off) - 1,
-                                   int(keep_at_most), C.byref(out))
+    if ambiguity or strands == "both":
+        opts = _PlaceOptions(int(bool(ambiguity)), int(strands == "both"))
+        rc = self._lib.ipkgpu_db_place_opts(self._h, db._h, int(sigma), int(k), C.c_float(log_eps), data.ctypes.data, off.ctypes.data,
+                                            len(off) - 1, int(keep_at_most), C.byref(opts), C.byref(out))
+    else:
+        rc = self._lib.ipkgpu_db_place(self._h, db._h, int(sigma), int(k), C.c_float(log_eps), data.ctypes.data, off.ctypes.data, len(off) - 1,
+                                       int(keep_at_most), C.byref(out))
     if rc != 0:
         raise self._err(rc)
     try:
@@ -1017,15 +1035,17 @@ def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, l
         self._lib.ipkgpu_placements_free(out)
 
 
-def _place(self, db, seqs, keep_at_most=7, sigma=None, k=None, log_eps=None):
+def _place(self, db, seqs, keep_at_most=7, sigma=None, k=None, log_eps=None, ambiguity=False, strands="given"):
     """ipkgpu_db_place: places the query sequences `seqs` (str or bytes each) on the database `db` of this engine -> Placements.
     sigma, k and log_eps default to those of the file a loaded database came from (its header's sequence type, k-mer size and
-    log_threshold(omega, sigma, k)); a database built in this process needs them given."""
+    log_threshold(omega, sigma, k)); a database built in this process needs them given.
+    ambiguity=True expands a window with one ambiguous symbol (N, R, Y, ...; amino acids B, Z, J, X) into its resolutions;
+    strands="both" places the reverse complement as well (DNA) and keeps the better strand (ipkgpu_db_place_opts in include/ipkgpu.h)."""
     raw = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
     off = np.zeros(len(raw) + 1, np.uint64)
     if raw:
         off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-    return _place_packed(self, db, b"".join(raw), off, keep_at_most, sigma, k, log_eps)
+    return _place_packed(self, db, b"".join(raw), off, keep_at_most, sigma, k, log_eps, ambiguity, strands)
 
 
 Engine.place_packed = _place_packed
