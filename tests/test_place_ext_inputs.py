@@ -179,12 +179,13 @@ def test_wrong_implementations_are_told_apart(variant):
     assert diff > 0
 
 
-def contributions():
+def contributions(cases=None, modes=None):
     """{(scores of the resolutions naming a branch, R)} over every ambiguous window of every case, on every strand a mode places."""
+    cases, modes = (xc.ALL_CASES, xc.MODES) if cases is None else (cases, modes)
     out = set()
-    for name, make in xc.ALL_CASES.items():
+    for name, make in cases.items():
         c = make()
-        both = any(s == "both" for a, s in xc.MODES[name] if a)
+        both = any(s == "both" for a, s in modes[name] if a)
         for s in c.queries:
             for seq in ([s, xo.revcomp(s)] if both else [s]):
                 for _, codes in xo.windows(seq, c.sigma, c.k):
@@ -200,12 +201,17 @@ def contributions():
     return out
 
 
-def test_rounding_margin_of_every_ambiguous_contribution():
+def rounding_margin(cases, modes, log_eps, at_least, but=()):
+    """Every ambiguous contribution of `cases` under the threshold `log_eps`: the oracle's y is the correctly rounded one and the
+    60-digit value lies at least 2^-44 from a binary32 rounding midpoint (`but`: contributions the caller checks by itself).
+    -> (contributions, the closest distance)."""
     D = decimal.Decimal
     margin = D(2) ** -44
-    E32 = float(np.float32(xc.LOG_EPS))
+    E32 = float(np.float32(log_eps))
     E = 10.0 ** E32
-    seen = contributions()
+    seen = contributions(cases, modes)
+    assert set(but) <= seen
+    seen -= set(but)
     closest = D(1)
     with decimal.localcontext() as ctx:
         ctx.prec = 60
@@ -228,5 +234,11 @@ def test_rounding_margin_of_every_ambiguous_contribution():
             closest = min(closest, d)
             assert d >= margin, (xs, R, float(d))
             assert abs(y) <= 10.5                               # (mixed_scores: at most 7 x 1.5 in magnitude)
-    print(f"{len(seen)} distinct ambiguous contributions; the closest to a binary32 rounding midpoint: {float(closest):.3e} (margin {float(margin):.3e})")
-    assert len(seen) > 1000
+    print(f"log_eps {float(E32)!r}: {len(seen)} distinct ambiguous contributions; the closest to a binary32 rounding midpoint: {float(closest):.3e} "
+          f"(margin {float(margin):.3e})")
+    assert len(seen) > at_least
+    return len(seen), closest
+
+
+def test_rounding_margin_of_every_ambiguous_contribution():
+    rounding_margin(xc.ALL_CASES, xc.MODES, xc.LOG_EPS, 1000)
