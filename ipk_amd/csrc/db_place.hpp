@@ -80,26 +80,14 @@ int place_prepare(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t bits)
 
 int place_launch(ipkgpu_ctx* ctx, const PlaceArgs& a, const PlaceExtArgs* x, uint32_t bits_per_symbol, bool global, uint32_t grid)
 {
-    if (x) {
-        const size_t lds = PLACE_EXT_TAB_BYTES + (global ? 0 : (size_t)a.b_pad * 12);
-        if (bits_per_symbol == 2) {
-            if (global) hipLaunchKernelGGL((place_ext_kernel<2, true>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
-            else hipLaunchKernelGGL((place_ext_kernel<2, false>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
-        } else {
-            if (global) hipLaunchKernelGGL((place_ext_kernel<5, true>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
-            else hipLaunchKernelGGL((place_ext_kernel<5, false>), dim3(grid), dim3(64), lds, ctx->stream, a, *x);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        return IPKGPU_OK;
-    }
-    const size_t lds = PLACE_SYMTAB_BYTES + (global ? 0 : (size_t)a.b_pad * 12);
-    if (bits_per_symbol == 2) {
-        if (global) hipLaunchKernelGGL((place_kernel<2, true>), dim3(grid), dim3(64), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((place_kernel<2, false>), dim3(grid), dim3(64), lds, ctx->stream, a);
-    } else {
-        if (global) hipLaunchKernelGGL((place_kernel<5, true>), dim3(grid), dim3(64), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((place_kernel<5, false>), dim3(grid), dim3(64), lds, ctx->stream, a);
-    }
+    // the block's LDS: the kernel's symbol tables, and S, C and the touched list behind them unless they are global
+    const size_t tables = global ? 0 : (size_t)a.b_pad * 12;
+    auto launch = [&](auto BITS_, auto GLOBAL_) {
+        if (x) hipLaunchKernelGGL((place_ext_kernel<BITS_, GLOBAL_>), dim3(grid), dim3(64), PLACE_EXT_TAB_BYTES + tables, ctx->stream, a, *x);
+        else hipLaunchKernelGGL((place_kernel<BITS_, GLOBAL_>), dim3(grid), dim3(64), PLACE_SYMTAB_BYTES + tables, ctx->stream, a);
+    };
+    if (bits_per_symbol == 2) global ? launch(int_c<2>{}, std::true_type{}) : launch(int_c<2>{}, std::false_type{});
+    else global ? launch(int_c<5>{}, std::true_type{}) : launch(int_c<5>{}, std::false_type{});
     HIP_TRY(ctx, hipGetLastError());
     return IPKGPU_OK;
 }

@@ -18,6 +18,7 @@
 //                          block (GLOBAL = true); the address space is fixed per instantiation, never a generic pointer.
 //                          Epilogue: over the touched branches only -- scores, a sorted top list of one 64-bit (score, branch) word
 //                          per lane, the f64 denominator; the same walk clears S and C for the workgroup's next query.
+//                          Each phase is one inlined function (place_tables .. place_store) that place_ext_kernel calls as well.
 #pragma once
 #include "../../include/ipkgpu.h"
 #include "dcla_device.hpp"
@@ -137,23 +138,201 @@ __device__ __forceinline__ uint64_t place_rank_word(float score, uint32_t branch
     return ((uint64_t)enc_score_bits(__float_as_uint(score)) << 32) | (uint64_t)(0xFFFFFFFFu - branch);
 }
 
+// ---- the phases of a placement: one text each, inlined into place_kernel and place_ext_kernel ------------------------------------------
+// S, C and touched are plain pointers whose address space the caller's GLOBAL fixes: the functions are inlined, so every instantiation
+// keeps its LDS or global instructions (no generic pointer, no FLAT instruction).
+
+// One pass over a query (one strand): the figures counted on the way, then what the epilogue leaves -- lane r's placement of rank r
+// (branch PLACE_NONE: none), the best score and the denominator of the likelihood weight ratios.
+struct PlacePass {
+    uint32_t W = 0, n_found = 0, n_touched = 0, n_amb = 0;
+    uint32_t branch = PLACE_NONE, count = 0;
+    float score = 0.0f, best = 0.0f;
+    double den = 0.0;
+};
+
+// S, C and the touched list of the workgroup: its slice of the global block, or the LDS behind the kernel's `tab_bytes` of symbol
+// tables, which are zeroed here (the global ones are zero on entry).  The caller syncs once its own tables are written as well.
+template <bool GLOBAL>
+__device__ __forceinline__ void place_tables(const PlaceArgs& a, unsigned char* lds, uint32_t tab_bytes, uint32_t lane, float*& S, uint32_t*& C,
+                                             uint32_t*& touched)
+{
+    if constexpr (GLOBAL) {
+        S = a.g_s + (size_t)blockIdx.x * a.b_pad; C = a.g_c + (size_t)blockIdx.x * a.b_pad; touched = a.g_touched + (size_t)blockIdx.x * a.b_pad;
+    } else {
+        S = reinterpret_cast<float*>(lds + tab_bytes);
+        C = reinterpret_cast<uint32_t*>(S + a.b_pad);
+        touched = C + a.b_pad;
+        for (uint32_t t = lane; t < a.b_pad; t += 64) { S[t] = 0.0f; C[t] = 0; }
+    }
+}
+
+// the code of the lane's window (k symbols of BITS bits from the lane's position on) out of the ballot planes of the symbols
+// s_lo (positions base + lane) and s_hi (base + 64 + lane)
+template <int BITS>
+__device__ __forceinline__ uint32_t place_window_code(uint32_t s_lo, uint32_t s_hi, uint32_t lane, uint32_t k)
+{
+    uint32_t plane[BITS];
+#pragma unroll
+    for (int p = 0; p < BITS; ++p) plane[p] = place_plane_at(ballot64((s_lo >> p) & 1u), ballot64((s_hi >> p) & 1u), lane);
+    uint32_t code = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        uint32_t sym = 0;
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) sym |= ((plane[p] >> i) & 1u) << p;
+        code = (code << BITS) | sym;
+    }
+    return code;
+}
+
+// the entry range of `code` if it is a key: a binary search inside its prefix's range of keys[]
+__device__ __forceinline__ bool place_lookup(const PlaceArgs& a, uint32_t code, uint64_t& off, uint32_t& cnt)
+{
+    const uint32_t j = code >> a.shift;
+    uint32_t lo = a.index[j];
+    const uint32_t end = a.index[j + 1];
+    uint32_t hi = end;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.keys[mid] < code) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && a.keys[lo] == code) {
+        off = a.key_off[lo];
+        cnt = (uint32_t)(a.key_off[lo + 1] - off);
+        return true;
+    }
+    return false;
+}
+
+// The lanes with v set add y to their branch b (distinct among them): S[b] += y, C[b] += 1, and a branch that had no contribution yet
+// joins the touched list.  Ends with the sync that lets the next call name these branches from other lanes.  (The ambiguous window's
+// P / c tables keep their own text of this: through here their f64 adds compiled to more SGPR spills, profiles/place_shared.txt.)
+__device__ __forceinline__ void place_add(float* S, uint32_t* C, uint32_t* touched, uint32_t& n_touched, bool v, uint32_t b, float y)
+{
+    bool fresh = false;
+    if (v) {
+        S[b] = S[b] + y;
+        const uint32_t c = C[b];
+        C[b] = c + 1;
+        fresh = c == 0;
+    }
+    const uint64_t fm = ballot64(fresh);
+    if (fresh) touched[n_touched + mbcnt(fm)] = b;
+    n_touched += (uint32_t)__popcll(fm);
+    wave_lds_sync();
+}
+
+// The windows of `todo` (bit w: lane w's window, entries [off, off + cnt) of that lane) in order, a window's entries 64 at a time,
+// the next tile loaded under this tile's adds: one branch's scores are added in window order.
+__device__ __forceinline__ void place_walk(const PlaceArgs& a, float* S, uint32_t* C, uint32_t* touched, uint32_t& n_touched, uint64_t todo,
+                                           uint64_t off, uint32_t cnt, uint32_t lane)
+{
+    uint64_t t_off = 0;
+    uint32_t t_cnt = 0, t_at = 0;
+    auto fetch = [&](uint2& e, bool& v) -> bool {
+        if (t_at >= t_cnt) {
+            if (todo == 0) return false;
+            const uint32_t w = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            t_off = place_readlane64(off, w);
+            t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cnt, (int)w);
+            t_at = 0;
+        }
+        v = t_at + lane < t_cnt;
+        e = v ? a.entries[t_off + t_at + lane] : make_uint2(0, 0);
+        t_at += 64;
+        return true;
+    };
+    uint2 cur; bool cur_v;
+    bool more = fetch(cur, cur_v);
+    while (more) {
+        uint2 nxt = make_uint2(0, 0); bool nxt_v = false;
+        more = fetch(nxt, nxt_v);
+        place_add(S, C, touched, n_touched, cur_v, cur.x, __uint_as_float(cur.y));
+        cur = nxt; cur_v = nxt_v;
+    }
+}
+
+// the best `keep` of the touched branches sorted across the lanes: lane r's word is rank r's (0: no such rank)
+__device__ __forceinline__ uint64_t place_top(const float* S, const uint32_t* C, const uint32_t* touched, uint32_t n_touched, uint32_t W,
+                                              float log_eps, uint32_t keep, uint32_t lane)
+{
+    uint64_t top = 0;
+    uint64_t kth = 0;                                                     // the word at rank keep - 1: what a candidate has to beat
+    for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
+        uint64_t word = 0;
+        if (i0 + lane < n_touched) {
+            const uint32_t b = touched[i0 + lane];
+            const float pen = (float)(W - C[b]) * log_eps;
+            word = place_rank_word(S[b] + pen, b);
+        }
+        uint64_t pend = ballot64(word > kth);
+        while (pend) {
+            const uint32_t src = (uint32_t)__builtin_ctzll(pend);
+            pend &= pend - 1;
+            const uint64_t w = place_readlane64(word, src);
+            if (w <= kth) continue;
+            const uint64_t prev = __shfl_up((unsigned long long)top, 1, 64);
+            if (w > top) top = (lane > 0 && w > prev) ? prev : w;
+            kth = place_readlane64(top, keep - 1);
+        }
+    }
+    return top;
+}
+
+// the denominator over ALL touched branches (f64, any order); S and C back to zero for the workgroup's next pass
+__device__ __forceinline__ double place_denominator(float* S, uint32_t* C, const uint32_t* touched, uint32_t n_touched, uint32_t W, float log_eps,
+                                                    float best, uint32_t lane)
+{
+    double den = 0.0;
+    for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
+        if (i0 + lane < n_touched) {
+            const uint32_t b = touched[i0 + lane];
+            const float pen = (float)(W - C[b]) * log_eps;
+            const float score = S[b] + pen;
+            den += exp10((double)score - (double)best);
+            S[b] = 0.0f; C[b] = 0;
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) den += __shfl_xor(den, s, 64);
+    wave_lds_sync();
+    return den;
+}
+
+// the epilogue of a pass, over the touched branches only: the lanes' placements out of the top list, then the denominator
+__device__ __forceinline__ void place_epilogue(const PlaceArgs& a, float* S, uint32_t* C, const uint32_t* touched, uint32_t lane, PlacePass& r)
+{
+    const uint64_t top = place_top(S, C, touched, r.n_touched, r.W, a.log_eps, a.keep, lane);
+    r.branch = top ? 0xFFFFFFFFu - (uint32_t)top : PLACE_NONE;
+    r.score = top ? __uint_as_float(dec_score_bits((uint32_t)(top >> 32))) : 0.0f;
+    r.count = top ? C[r.branch] : 0;
+    r.best = __uint_as_float(dec_score_bits((uint32_t)(place_readlane64(top, 0) >> 32)));
+    wave_lds_sync();
+    r.den = place_denominator(S, C, touched, r.n_touched, r.W, a.log_eps, r.best, lane);
+}
+
+// query q's results: lane r writes rank r, lane 0 the query's figures
+__device__ __forceinline__ void place_store(const PlaceArgs& a, uint32_t q, uint32_t lane, const PlacePass& r)
+{
+    if (lane < a.keep) {
+        const size_t o = (size_t)q * a.keep + lane;
+        a.out_branch[o] = r.branch;
+        a.out_score[o] = r.score;
+        a.out_count[o] = r.count;
+        a.out_lwr[o] = r.branch != PLACE_NONE ? exp10((double)r.score - (double)r.best) / r.den : 0.0;
+    }
+    if (lane == 0) { a.out_n_kmers[q] = r.W; a.out_n_found[q] = r.n_found; a.out_n_branches[q] = r.n_touched; }
+}
+
 template <int BITS, bool GLOBAL>
 __global__ __launch_bounds__(64) void place_kernel(PlaceArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char place_lds[];
     unsigned char* symtab = place_lds;
-    float* S; uint32_t* C; uint32_t* touched;
-    if constexpr (GLOBAL) {
-        S = a.g_s + (size_t)blockIdx.x * a.b_pad; C = a.g_c + (size_t)blockIdx.x * a.b_pad; touched = a.g_touched + (size_t)blockIdx.x * a.b_pad;
-    } else {
-        S = reinterpret_cast<float*>(place_lds + PLACE_SYMTAB_BYTES);
-        C = reinterpret_cast<uint32_t*>(S + a.b_pad);
-        touched = C + a.b_pad;
-    }
     const uint32_t lane = lane_id();
     for (uint32_t t = lane; t < 256; t += 64) symtab[t] = (unsigned char)place_symbol(a.sigma, t);
-    if constexpr (!GLOBAL)
-        for (uint32_t t = lane; t < a.b_pad; t += 64) { S[t] = 0.0f; C[t] = 0; }
+    float* S; uint32_t* C; uint32_t* touched;
+    place_tables<GLOBAL>(a, place_lds, PLACE_SYMTAB_BYTES, lane, S, C, touched);
     wave_lds_sync();
     const uint32_t k = a.k, mask_k = (1u << k) - 1u;
 
@@ -161,7 +340,7 @@ __global__ __launch_bounds__(64) void place_kernel(PlaceArgs a)
         const uint64_t q0 = a.seq_off[q] - a.seq_base;
         const uint32_t n = (uint32_t)(a.seq_off[q + 1] - a.seq_base - q0);
         const unsigned char* seq = a.seqs + q0;
-        uint32_t W = 0, n_found = 0, n_touched = 0;
+        PlacePass r;
 
         for (uint64_t base = 0; base + k <= n; base += 64) {
             // ---- phase one: the codes of windows base .. base + 63 out of bit planes, and their lookup
@@ -170,131 +349,28 @@ __global__ __launch_bounds__(64) void place_kernel(PlaceArgs a)
             const uint32_t s_hi = (lane + 1 < k && p1 < n) ? symtab[seq[p1]] : 0xFFu;
             const uint32_t valid_bits = place_plane_at(ballot64(s_lo != 0xFFu), ballot64(s_hi != 0xFFu), lane);
             const bool win = (valid_bits & mask_k) == mask_k;            // (a window that runs past the end meets an invalid symbol there)
-            uint32_t plane[BITS];
-#pragma unroll
-            for (int p = 0; p < BITS; ++p) plane[p] = place_plane_at(ballot64((s_lo >> p) & 1u), ballot64((s_hi >> p) & 1u), lane);
-            uint32_t code = 0;
-            for (uint32_t i = 0; i < k; ++i) {
-                uint32_t sym = 0;
-#pragma unroll
-                for (int p = 0; p < BITS; ++p) sym |= ((plane[p] >> i) & 1u) << p;
-                code = (code << BITS) | sym;
-            }
+            const uint32_t code = place_window_code<BITS>(s_lo, s_hi, lane, k);
             uint64_t off = 0;
             uint32_t cnt = 0;
             bool found = false;
-            if (win) {
-                const uint32_t j = code >> a.shift;
-                uint32_t lo = a.index[j];
-                const uint32_t end = a.index[j + 1];
-                uint32_t hi = end;
-                while (lo < hi) {
-                    const uint32_t mid = lo + (hi - lo) / 2;
-                    if (a.keys[mid] < code) lo = mid + 1; else hi = mid;
-                }
-                if (lo < end && a.keys[lo] == code) {
-                    found = true;
-                    off = a.key_off[lo];
-                    cnt = (uint32_t)(a.key_off[lo + 1] - off);
-                }
-            }
-            W += (uint32_t)__popcll(ballot64(win));
-            n_found += (uint32_t)__popcll(ballot64(found));
-
-            // ---- phase two: the windows in order, a window's entries 64 at a time, the next tile loaded under this tile's adds
-            uint64_t todo = ballot64(cnt != 0);
-            uint64_t t_off = 0;
-            uint32_t t_cnt = 0, t_at = 0;
-            auto fetch = [&](uint2& e, bool& v) -> bool {
-                if (t_at >= t_cnt) {
-                    if (todo == 0) return false;
-                    const uint32_t w = (uint32_t)__builtin_ctzll(todo);
-                    todo &= todo - 1;
-                    t_off = place_readlane64(off, w);
-                    t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cnt, (int)w);
-                    t_at = 0;
-                }
-                v = t_at + lane < t_cnt;
-                e = v ? a.entries[t_off + t_at + lane] : make_uint2(0, 0);
-                t_at += 64;
-                return true;
-            };
-            uint2 cur; bool cur_v;
-            bool more = fetch(cur, cur_v);
-            while (more) {
-                uint2 nxt = make_uint2(0, 0); bool nxt_v = false;
-                more = fetch(nxt, nxt_v);
-                bool fresh = false;
-                if (cur_v) {
-                    S[cur.x] = S[cur.x] + __uint_as_float(cur.y);
-                    const uint32_t c = C[cur.x];
-                    C[cur.x] = c + 1;
-                    fresh = c == 0;
-                }
-                const uint64_t fm = ballot64(fresh);
-                if (fresh) touched[n_touched + mbcnt(fm)] = cur.x;
-                n_touched += (uint32_t)__popcll(fm);
-                wave_lds_sync();                                          // (the next tile may name these branches from other lanes)
-                cur = nxt; cur_v = nxt_v;
-            }
+            if (win) found = place_lookup(a, code, off, cnt);
+            r.W += (uint32_t)__popcll(ballot64(win));
+            r.n_found += (uint32_t)__popcll(ballot64(found));
+            // ---- phase two: the found windows in order
+            place_walk(a, S, C, touched, r.n_touched, ballot64(cnt != 0), off, cnt, lane);
         }
-
-        // ---- epilogue: scores of the touched branches, the best `keep` of them sorted across the lanes (lane r = rank r)
-        uint64_t top = 0;
-        uint64_t kth = 0;                                                 // the word at rank keep - 1: what a candidate has to beat
-        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
-            const bool v = i0 + lane < n_touched;
-            uint64_t word = 0;
-            if (v) {
-                const uint32_t b = touched[i0 + lane];
-                const float pen = (float)(W - C[b]) * a.log_eps;
-                word = place_rank_word(S[b] + pen, b);
-            }
-            uint64_t pend = ballot64(word > kth);
-            while (pend) {
-                const uint32_t src = (uint32_t)__builtin_ctzll(pend);
-                pend &= pend - 1;
-                const uint64_t w = place_readlane64(word, src);
-                if (w <= kth) continue;
-                const uint64_t prev = __shfl_up((unsigned long long)top, 1, 64);
-                if (w > top) top = (lane > 0 && w > prev) ? prev : w;
-                kth = place_readlane64(top, a.keep - 1);
-            }
-        }
-        const uint32_t my_branch = top ? 0xFFFFFFFFu - (uint32_t)top : PLACE_NONE;
-        const float my_score = top ? __uint_as_float(dec_score_bits((uint32_t)(top >> 32))) : 0.0f;
-        const uint32_t my_count = top ? C[my_branch] : 0;
-        const float best = __uint_as_float(dec_score_bits((uint32_t)(place_readlane64(top, 0) >> 32)));
-        wave_lds_sync();
-        // the denominator over ALL touched branches (f64, any order); S and C back to zero for the next query
-        double den = 0.0;
-        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
-            if (i0 + lane < n_touched) {
-                const uint32_t b = touched[i0 + lane];
-                const float pen = (float)(W - C[b]) * a.log_eps;
-                const float score = S[b] + pen;
-                den += exp10((double)score - (double)best);
-                S[b] = 0.0f; C[b] = 0;
-            }
-        }
-        for (int s = 32; s > 0; s >>= 1) den += __shfl_xor(den, s, 64);
-        wave_lds_sync();
-        if (lane < a.keep) {
-            const size_t o = (size_t)q * a.keep + lane;
-            a.out_branch[o] = my_branch;
-            a.out_score[o] = my_score;
-            a.out_count[o] = my_count;
-            a.out_lwr[o] = top ? exp10((double)my_score - (double)best) / den : 0.0;
-        }
-        if (lane == 0) { a.out_n_kmers[q] = W; a.out_n_found[q] = n_found; a.out_n_branches[q] = n_touched; }
+        place_epilogue(a, S, C, touched, lane, r);
+        place_store(a, q, lane, r);
     }
 }
 
 // ---- the extended modes (ipkgpu_db_place_opts): ambiguous symbols expanded, both strands --------------------------------------------
-// place_ext_kernel is place_kernel's sibling: the same phases in the same order with the additions below.  place_kernel's own text
-// stays as it was, so a call without options launches the code it launched before: its phases moved into a body shared by both kernels
-// compiled to other registers (SGPR spills 3 -> 196 in place_kernel<2, true>; profiles/place_ext.txt), and no placement rate has been
-// measured that could say what that costs.  A change to a phase of one kernel belongs in the other as well.
+// place_ext_kernel is place_kernel's sibling.  Every phase the two have in common is one of the functions above, called by both: the
+// table prologue, the window codes, the lookup, the ordered tile walk and the add it is made of, the top list, the denominator and
+// the result stores.  The kernels themselves stay two, each with its own loops and nothing in a shared loop that asks which kernel
+// runs it: place_kernel as an instantiation of this body with the additions compiled out took its SGPR spills from 3 to 196
+// (place_kernel<2, true>; profiles/place_ext.txt, "tried and dropped"), while with the shared functions no instantiation of either
+// kernel spills more or holds fewer wavefronts than it did with its own text (profiles/place_shared.txt).
 //
 //   tables     symtab[2][256]: the symbol code of a byte on the given strand and, complemented (3 - code), on the reverse strand;
 //              0xFE: an ambiguous symbol (with ambiguity on), 0xFF: invalid.  masktab[2][32]: the resolution mask (bit c = symbol code c)
@@ -310,8 +386,9 @@ __global__ __launch_bounds__(64) void place_kernel(PlaceArgs a)
 //              y = (float)log10((P + (R - c) E) / R) into S and C and are cleared for the next window
 //   tables P, c, touched-by-the-window: 16 bytes per branch in the workgroup's slice of a global block for BOTH variants (ambiguous
 //              windows are the rare ones: a read with one N has k of them), so LDS holds what it held
-//   strands    the wavefront runs the query twice; the first pass's lane results and figures wait in registers, the epilogue of each pass
-//              leaves S and C zero, and the winner is written (the reverse strand iff it is placed and the given one is not or scores less)
+//   strands    the wavefront runs the query twice, the epilogue of each pass leaves S and C zero; the given strand's results are
+//              written after its pass and only "placed at all" and its best score wait in registers: the reverse strand's pass
+//              writes over them iff it wins (it is placed and the given strand is not or scores less)
 constexpr uint32_t PLACE_SYM_AMBIGUOUS = 0xFEu;
 constexpr uint32_t PLACE_EXT_TAB_BYTES = 2 * 256 + 2 * 32 * 4;
 
@@ -343,38 +420,11 @@ struct PlaceExtArgs {
     uint32_t* out_strand; uint32_t* out_n_ambiguous;                     // [n_queries]
 };
 
-// position lo of keys[] and the entry range of `code` if it is a key
-__device__ __forceinline__ bool place_lookup(const PlaceArgs& a, uint32_t code, uint64_t& off, uint32_t& cnt)
-{
-    const uint32_t j = code >> a.shift;
-    uint32_t lo = a.index[j];
-    const uint32_t end = a.index[j + 1];
-    uint32_t hi = end;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.keys[mid] < code) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && a.keys[lo] == code) {
-        off = a.key_off[lo];
-        cnt = (uint32_t)(a.key_off[lo + 1] - off);
-        return true;
-    }
-    return false;
-}
-
 template <int BITS, bool GLOBAL>
 __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs x)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char place_lds[];
     unsigned char* symtab = place_lds;
-    float* S; uint32_t* C; uint32_t* touched;
-    if constexpr (GLOBAL) {
-        S = a.g_s + (size_t)blockIdx.x * a.b_pad; C = a.g_c + (size_t)blockIdx.x * a.b_pad; touched = a.g_touched + (size_t)blockIdx.x * a.b_pad;
-    } else {
-        S = reinterpret_cast<float*>(place_lds + PLACE_EXT_TAB_BYTES);
-        C = reinterpret_cast<uint32_t*>(S + a.b_pad);
-        touched = C + a.b_pad;
-    }
     const uint32_t lane = lane_id();
     uint32_t* masktab = reinterpret_cast<uint32_t*>(place_lds + 512);
     for (uint32_t t = lane; t < 256; t += 64) {
@@ -388,8 +438,8 @@ __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs
         masktab[lane] = m;
         masktab[32 + lane] = ((m & 1u) << 3) | ((m & 2u) << 1) | ((m & 4u) >> 1) | ((m & 8u) >> 3);
     }
-    if constexpr (!GLOBAL)
-        for (uint32_t t = lane; t < a.b_pad; t += 64) { S[t] = 0.0f; C[t] = 0; }
+    float* S; uint32_t* C; uint32_t* touched;
+    place_tables<GLOBAL>(a, place_lds, PLACE_EXT_TAB_BYTES, lane, S, C, touched);
     wave_lds_sync();
     const uint32_t k = a.k, mask_k = (1u << k) - 1u;
 
@@ -397,84 +447,34 @@ __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs
         const uint64_t q0 = a.seq_off[q] - a.seq_base;
         const uint32_t n = (uint32_t)(a.seq_off[q + 1] - a.seq_base - q0);
         const unsigned char* seq = a.seqs + q0;
-        // what the given strand's pass found, kept while the reverse strand's runs
-        uint32_t g_branch = PLACE_NONE, g_count = 0, g_W = 0, g_found = 0, g_touched = 0, g_amb = 0;
-        float g_score = 0.0f, g_best = 0.0f;
-        double g_den = 0.0;
-        bool g_placed = false;
-        const uint32_t n_pass = 1u + x.strands;
+        bool given_any = false;                                          // the given strand's pass: has it a placement, and its best score
+        float given_best = 0.0f;
 
-        for (uint32_t pass = 0; pass < n_pass; ++pass) {
-        const unsigned char* tab = symtab + pass * 256u;
-        // byte p of the strand this pass places
-        auto at = [&](uint64_t p) -> uint32_t { return pass ? seq[n - 1 - p] : seq[p]; };
-        uint32_t W = 0, n_found = 0, n_touched = 0, n_amb = 0;
+        for (uint32_t pass = 0; pass <= x.strands; ++pass) {
+            const unsigned char* tab = symtab + pass * 256u;
+            // byte p of the strand this pass places
+            auto at = [&](uint64_t p) -> uint32_t { return pass ? seq[n - 1 - p] : seq[p]; };
+            PlacePass r;
 
-        for (uint64_t base = 0; base + k <= n; base += 64) {
-            // ---- phase one: the codes of windows base .. base + 63 out of bit planes, and their lookup
-            const uint64_t p0 = base + lane, p1 = base + 64 + lane;
-            const uint32_t s_lo = p0 < n ? tab[at(p0)] : 0xFFu;
-            const uint32_t s_hi = (lane + 1 < k && p1 < n) ? tab[at(p1)] : 0xFFu;
-            const uint32_t valid_bits = place_plane_at(ballot64(s_lo != 0xFFu), ballot64(s_hi != 0xFFu), lane);
-            bool win = (valid_bits & mask_k) == mask_k;                  // (a window that runs past the end meets an invalid symbol there)
-            const uint32_t amb_bits = place_plane_at(ballot64(s_lo == PLACE_SYM_AMBIGUOUS), ballot64(s_hi == PLACE_SYM_AMBIGUOUS), lane) & mask_k;
-            const bool amb = win && __popc(amb_bits) == 1;
-            win = win && amb_bits == 0;
-            uint32_t plane[BITS];
-#pragma unroll
-            for (int p = 0; p < BITS; ++p) plane[p] = place_plane_at(ballot64((s_lo >> p) & 1u), ballot64((s_hi >> p) & 1u), lane);
-            uint32_t code = 0;
-            for (uint32_t i = 0; i < k; ++i) {
-                uint32_t sym = 0;
-#pragma unroll
-                for (int p = 0; p < BITS; ++p) sym |= ((plane[p] >> i) & 1u) << p;
-                code = (code << BITS) | sym;
-            }
-            uint64_t off = 0;
-            uint32_t cnt = 0;
-            bool found = false;
-            if (win) found = place_lookup(a, code, off, cnt);
-            W += (uint32_t)__popcll(ballot64(win));
-            n_found += (uint32_t)__popcll(ballot64(found));
+            for (uint64_t base = 0; base + k <= n; base += 64) {
+                // ---- phase one: the codes of windows base .. base + 63 out of bit planes, and their lookup
+                const uint64_t p0 = base + lane, p1 = base + 64 + lane;
+                const uint32_t s_lo = p0 < n ? tab[at(p0)] : 0xFFu;
+                const uint32_t s_hi = (lane + 1 < k && p1 < n) ? tab[at(p1)] : 0xFFu;
+                const uint32_t valid_bits = place_plane_at(ballot64(s_lo != 0xFFu), ballot64(s_hi != 0xFFu), lane);
+                bool win = (valid_bits & mask_k) == mask_k;                  // (a window that runs past the end meets an invalid symbol there)
+                const uint32_t amb_bits = place_plane_at(ballot64(s_lo == PLACE_SYM_AMBIGUOUS), ballot64(s_hi == PLACE_SYM_AMBIGUOUS), lane) & mask_k;
+                const bool amb = win && __popc(amb_bits) == 1;
+                win = win && amb_bits == 0;
+                uint32_t code = place_window_code<BITS>(s_lo, s_hi, lane, k);
+                uint64_t off = 0;
+                uint32_t cnt = 0;
+                bool found = false;
+                if (win) found = place_lookup(a, code, off, cnt);
+                r.W += (uint32_t)__popcll(ballot64(win));
+                r.n_found += (uint32_t)__popcll(ballot64(found));
 
-            // ---- phase two: the windows in order, a window's entries 64 at a time, the next tile loaded under this tile's adds
-            auto walk = [&](uint64_t todo) {
-                uint64_t t_off = 0;
-                uint32_t t_cnt = 0, t_at = 0;
-                auto fetch = [&](uint2& e, bool& v) -> bool {
-                    if (t_at >= t_cnt) {
-                        if (todo == 0) return false;
-                        const uint32_t w = (uint32_t)__builtin_ctzll(todo);
-                        todo &= todo - 1;
-                        t_off = place_readlane64(off, w);
-                        t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cnt, (int)w);
-                        t_at = 0;
-                    }
-                    v = t_at + lane < t_cnt;
-                    e = v ? a.entries[t_off + t_at + lane] : make_uint2(0, 0);
-                    t_at += 64;
-                    return true;
-                };
-                uint2 cur; bool cur_v;
-                bool more = fetch(cur, cur_v);
-                while (more) {
-                    uint2 nxt = make_uint2(0, 0); bool nxt_v = false;
-                    more = fetch(nxt, nxt_v);
-                    bool fresh = false;
-                    if (cur_v) {
-                        S[cur.x] = S[cur.x] + __uint_as_float(cur.y);
-                        const uint32_t c = C[cur.x];
-                        C[cur.x] = c + 1;
-                        fresh = c == 0;
-                    }
-                    const uint64_t fm = ballot64(fresh);
-                    if (fresh) touched[n_touched + mbcnt(fm)] = cur.x;
-                    n_touched += (uint32_t)__popcll(fm);
-                    wave_lds_sync();                                      // (the next tile may name these branches from other lanes)
-                    cur = nxt; cur_v = nxt_v;
-                }
-            };
-            {
+                // ---- phase two: the windows in order, the exact ones as place_kernel walks them, an ambiguous one through P
                 double* P = x.g_p + (size_t)blockIdx.x * a.b_pad;
                 uint32_t* WC = x.g_wc + (size_t)blockIdx.x * a.b_pad;
                 uint32_t* wtouched = x.g_wtouched + (size_t)blockIdx.x * a.b_pad;
@@ -488,13 +488,13 @@ __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs
                     a_mask = masks[at(base + lane + pos) & 31u];
                 }
                 uint64_t todo = ballot64(cnt != 0), ambiguous = ballot64(amb);
-                W += (uint32_t)__popcll(ambiguous);
-                n_amb += (uint32_t)__popcll(ambiguous);
+                r.W += (uint32_t)__popcll(ambiguous);
+                r.n_amb += (uint32_t)__popcll(ambiguous);
                 while (ambiguous) {
                     const uint32_t w = (uint32_t)__builtin_ctzll(ambiguous);
                     ambiguous &= ambiguous - 1;
                     const uint64_t below = (1ull << w) - 1ull;
-                    if (todo & below) walk(todo & below);                 // the exact windows before it, in order
+                    place_walk(a, S, C, touched, r.n_touched, todo & below, off, cnt, lane);   // the exact windows before it, in order
                     todo &= ~below;
                     // window w: resolution r (ascending symbol code) is lane r's
                     const uint32_t w_code = (uint32_t)__builtin_amdgcn_readlane((int)code, (int)w);
@@ -508,14 +508,14 @@ __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs
                     uint32_t r_cnt = 0;
                     bool r_found = false;
                     if (lane < R) r_found = place_lookup(a, w_code | (sym << w_shift), r_off, r_cnt);
-                    n_found += ballot64(r_found) != 0 ? 1u : 0u;
+                    r.n_found += ballot64(r_found) != 0 ? 1u : 0u;
                     uint64_t keys_todo = ballot64(r_cnt != 0);
                     uint32_t n_wt = 0;
                     while (keys_todo) {                                   // one resolution after the other: P's order is the definition's
-                        const uint32_t r = (uint32_t)__builtin_ctzll(keys_todo);
+                        const uint32_t res = (uint32_t)__builtin_ctzll(keys_todo);
                         keys_todo &= keys_todo - 1;
-                        const uint64_t t_off = place_readlane64(r_off, r);
-                        const uint32_t t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)r_cnt, (int)r);
+                        const uint64_t t_off = place_readlane64(r_off, res);
+                        const uint32_t t_cnt = (uint32_t)__builtin_amdgcn_readlane((int)r_cnt, (int)res);
                         for (uint32_t t0 = 0; t0 < t_cnt; t0 += 64) {
                             bool fresh = false;
                             uint32_t b = 0;
@@ -534,98 +534,30 @@ __global__ __launch_bounds__(64) void place_ext_kernel(PlaceArgs a, PlaceExtArgs
                         }
                     }
                     for (uint32_t i0 = 0; i0 < n_wt; i0 += 64) {          // the window's branches get y; its tables go back to zero
-                        bool fresh = false;
+                        const bool v = i0 + lane < n_wt;
                         uint32_t b = 0;
-                        if (i0 + lane < n_wt) {
+                        float y = 0.0f;
+                        if (v) {
                             b = wtouched[i0 + lane];
-                            const uint32_t c = WC[b];
-                            double p = P[b];
-                            p = p + (double)(R - c) * x.E;
-                            const float y = (float)log10(p / (double)R);
-                            S[b] = S[b] + y;
-                            const uint32_t cc = C[b];
-                            C[b] = cc + 1;
-                            fresh = cc == 0;
+                            const double p = P[b] + (double)(R - WC[b]) * x.E;
+                            y = (float)log10(p / (double)R);
                             P[b] = 0.0; WC[b] = 0;
                         }
-                        const uint64_t fm = ballot64(fresh);
-                        if (fresh) touched[n_touched + mbcnt(fm)] = b;
-                        n_touched += (uint32_t)__popcll(fm);
-                        wave_lds_sync();
+                        place_add(S, C, touched, r.n_touched, v, b, y);
                     }
                 }
-                if (todo) walk(todo);
+                place_walk(a, S, C, touched, r.n_touched, todo, off, cnt, lane);
             }
-        }
 
-        // ---- epilogue: scores of the touched branches, the best `keep` of them sorted across the lanes (lane r = rank r)
-        uint64_t top = 0;
-        uint64_t kth = 0;                                                 // the word at rank keep - 1: what a candidate has to beat
-        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
-            const bool v = i0 + lane < n_touched;
-            uint64_t word = 0;
-            if (v) {
-                const uint32_t b = touched[i0 + lane];
-                const float pen = (float)(W - C[b]) * a.log_eps;
-                word = place_rank_word(S[b] + pen, b);
+            place_epilogue(a, S, C, touched, lane, r);
+            // the reverse strand's results replace the given strand's iff it has a placement and the given strand has none or a
+            // smaller best score (as floats)
+            const bool any = (uint32_t)__builtin_amdgcn_readlane((int)r.branch, 0) != PLACE_NONE;
+            if (pass == 0 || (any && (!given_any || r.best > given_best))) {
+                place_store(a, q, lane, r);
+                if (lane == 0) { x.out_strand[q] = pass; x.out_n_ambiguous[q] = r.n_amb; }
             }
-            uint64_t pend = ballot64(word > kth);
-            while (pend) {
-                const uint32_t src = (uint32_t)__builtin_ctzll(pend);
-                pend &= pend - 1;
-                const uint64_t w = place_readlane64(word, src);
-                if (w <= kth) continue;
-                const uint64_t prev = __shfl_up((unsigned long long)top, 1, 64);
-                if (w > top) top = (lane > 0 && w > prev) ? prev : w;
-                kth = place_readlane64(top, a.keep - 1);
-            }
-        }
-        uint32_t my_branch = top ? 0xFFFFFFFFu - (uint32_t)top : PLACE_NONE;
-        float my_score = top ? __uint_as_float(dec_score_bits((uint32_t)(top >> 32))) : 0.0f;
-        uint32_t my_count = top ? C[my_branch] : 0;
-        float best = __uint_as_float(dec_score_bits((uint32_t)(place_readlane64(top, 0) >> 32)));
-        wave_lds_sync();
-        // the denominator over ALL touched branches (f64, any order); S and C back to zero for the next query
-        double den = 0.0;
-        for (uint32_t i0 = 0; i0 < n_touched; i0 += 64) {
-            if (i0 + lane < n_touched) {
-                const uint32_t b = touched[i0 + lane];
-                const float pen = (float)(W - C[b]) * a.log_eps;
-                const float score = S[b] + pen;
-                den += exp10((double)score - (double)best);
-                S[b] = 0.0f; C[b] = 0;
-            }
-        }
-        for (int s = 32; s > 0; s >>= 1) den += __shfl_xor(den, s, 64);
-        wave_lds_sync();
-        bool placed = top != 0;
-        uint32_t strand = 0;
-        {
-            if (x.strands) {
-                if (pass == 0) {
-                    g_branch = my_branch; g_score = my_score; g_count = my_count; g_best = best; g_den = den; g_placed = placed;
-                    g_W = W; g_found = n_found; g_touched = n_touched; g_amb = n_amb;
-                    continue;
-                }
-                // the reverse strand iff it has a placement and the given strand has none or a smaller best score (as floats)
-                const bool r_any = place_readlane64(top, 0) != 0;
-                const bool g_any = ballot64(g_placed) & 1ull;
-                if (r_any && (!g_any || best > g_best)) strand = 1;
-                else {
-                    my_branch = g_branch; my_score = g_score; my_count = g_count; best = g_best; den = g_den; placed = g_placed;
-                    W = g_W; n_found = g_found; n_touched = g_touched; n_amb = g_amb;
-                }
-            }
-        }
-        if (lane < a.keep) {
-            const size_t o = (size_t)q * a.keep + lane;
-            a.out_branch[o] = my_branch;
-            a.out_score[o] = my_score;
-            a.out_count[o] = my_count;
-            a.out_lwr[o] = placed ? exp10((double)my_score - (double)best) / den : 0.0;
-        }
-        if (lane == 0) { a.out_n_kmers[q] = W; a.out_n_found[q] = n_found; a.out_n_branches[q] = n_touched; }
-        if (lane == 0) { x.out_strand[q] = strand; x.out_n_ambiguous[q] = n_amb; }
+            given_any = any; given_best = r.best;
         }
     }
 }

@@ -72,7 +72,7 @@ def probe(out_path, n_groups, db_file, read_counts, ambiguity=False, strands="gi
         walls, kernels = [], []
         for rep in range(6):                                             # one warm-up, five timed
             t0 = time.time()
-            res = eng.place_packed(db, reads, off, keep_at_most=7, sigma=sigma, k=k, log_eps=eps, ambiguity=ambiguity, strands=strands)
+            res = eng.place_packed(db, reads.reshape(-1), off, keep_at_most=7, sigma=sigma, k=k, log_eps=eps, ambiguity=ambiguity, strands=strands)
             wall = time.time() - t0
             if first:
                 lines.append(f"first call on the database: index build (prefix table, branch count, duplicate check) {res.time_ms['index']:.3f} ms; "
@@ -96,7 +96,7 @@ def probe(out_path, n_groups, db_file, read_counts, ambiguity=False, strands="gi
     ext = ambiguity or strands == "both"
     want = xo.place(view, seqs, sigma, k, eps, 7, ambiguity, strands) if ext else po.place(view, seqs, sigma, k, eps, 7)
     t = time.time() - t0
-    sub = eng.place_packed(db, check[0], np.arange(len(seqs) + 1, dtype=np.uint64) * READ, keep_at_most=7, sigma=sigma, k=k, log_eps=eps,
+    sub = eng.place_packed(db, check[0].reshape(-1), np.arange(len(seqs) + 1, dtype=np.uint64) * READ, keep_at_most=7, sigma=sigma, k=k, log_eps=eps,
                            ambiguity=ambiguity, strands=strands)
     (xo.check if ext else po.check)(sub, want)
     lines.append(f"host oracle (tests/place{'_ext' if ext else ''}_oracle.py, one core), {len(seqs)} of the reads: {t:.3f} s = {len(seqs) / t:.0f} reads/s; the device's placements of them "
