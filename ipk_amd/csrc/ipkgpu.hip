@@ -141,6 +141,8 @@ struct ipkgpu_ctx {
     std::vector<uint32_t> h_branch;     // host copy of the last call's branch ids (source of an asynchronous upload)
     uint32_t comp_nb = 0, comp_stride = 0, comp_tbl = 0;
     double pairs_per_window = 0;      // calibration of the pair pool from the previous call
+    uint64_t count_pass_pairs = 0;    // what the count-only pre-pass of the context's first call counted (tests): pairs ...
+    uint64_t count_pass_queued = 0;   // ... and windows it queued for the big-list kernel instead
     double acc_main_ms = 0, acc_reduce_ms = 0;   // dominant scoring kernel / LDS reduce pass of the current call
     double acc_count_ms = 0, acc_write_ms = 0, acc_km_ms = 0;   // exact-partition count / write pass, key-major writer
     const char* main_kernel = "";                // name of the dominant kernel of the last scoring call
@@ -1497,6 +1499,7 @@ int score_batch_impl(ipkgpu_ctx* ctx, const Plan& pl, const float* logp_dev, uin
         HIP_TRY(ctx, hipMemcpyAsync(&se, p.emitted, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(&so, p.ovf_count, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->count_pass_pairs = se; ctx->count_pass_queued = so;
         const uint64_t s_windows = (uint64_t)slist.size() * pl.nwin;
         // windows that went to the big-list queue were not counted: assume they carry CAP^2 / 4 pairs each (generous)
         const double cap_pairs = 0.25 * (double)pl.geo.fast_cap * (double)pl.geo.fast_cap;
@@ -3196,6 +3199,8 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "place_batch_queries")) { *value = ctx->opt_place_batch; return IPKGPU_OK; }
     if (!strcmp(name, "place_lds_branches")) { *value = ctx->opt_place_lds; return IPKGPU_OK; }
     if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
+    if (!strcmp(name, "debug_count_pass_pairs")) { *value = (int64_t)ctx->count_pass_pairs; return IPKGPU_OK; }
+    if (!strcmp(name, "debug_count_pass_queued")) { *value = (int64_t)ctx->count_pass_queued; return IPKGPU_OK; }
     if (!strcmp(name, "debug_pool_bytes")) { *value = (int64_t)ctx->pool.cap; return IPKGPU_OK; }   // bytes the pair pool holds (tests)
     return IPKGPU_ERR_INVALID;
 }

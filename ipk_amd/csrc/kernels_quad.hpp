@@ -105,45 +105,93 @@ __device__ __forceinline__ void quad_node_thresholds(const float* bs, float e, f
     }
 }
 
-// One step: the H-symbol node of every 16-lane slot.  `base` = LDS float index of the node's first column of the
-// slot's window (cols[(window + J) * 4]); th = the node's thresholds; list = the node's list of the slot's window;
-// code16 = l16 * cmul.  Sub-step i's survivors follow sub-step i-1's in the list (ascending code order).
+// (x << 3) + y as ONE instruction (left to itself the compiler shares x << 3 with the rarely taken chunk-roll path and adds separately)
+__device__ __forceinline__ uint32_t lshl3_add(uint32_t x, uint32_t y)
+{
+    uint32_t r;
+    asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+// The LDS byte address of p (what a DS instruction takes).
+__device__ __forceinline__ uint32_t lds_addr(const void* p)
+{
+    typedef const char __attribute__((address_space(3)))* lds_ptr;
+    return (uint32_t)(uintptr_t)(lds_ptr)p;
+}
+// One 8-byte entry per lane of `mask` into LDS at `addr` + IMM (the ds_write form of store8_lanes, dcla_device.hpp; IMM, a constant
+// number of bytes, rides in the store's offset field): the lanes are selected by writing exec directly, so a compacting store needs
+// no per-lane predicate (the ballot that ranks the lanes IS the store's mask), no and-saveexec / branch / restore, and the compiler
+// keeps no second, per-lane copy of the and-chain behind the ballot.  From code that runs with ALL lanes enabled.  (DS operations of
+// a wave execute in issue order and the "memory" clobber keeps the compiler's own around it; its wait counts only ever over-wait
+// for an operation it does not know of.)
+template <uint32_t IMM = 0>
+__device__ __forceinline__ void lds_put8_lanes(uint32_t addr, uint32_t x, uint32_t y, uint64_t mask)
+{
+    static_assert(IMM < 65536 && IMM % 8 == 0, "the offset must fit the store's 16-bit field");
+    u32x2_t data; data.x = x; data.y = y;
+    IPK_ASSERT_FULL_EXEC();
+    asm volatile("s_mov_b64 exec, %2\n\tds_write_b64 %0, %1 offset:%3\n\ts_mov_b64 exec, -1" : : "v"(addr), "v"(data), "s"(mask), "n"(IMM) : "memory");
+}
+// Entry j of the list at the wave-uniform LDS address `base`: the address is ONE instruction, (j << 3) + base with the base as its
+// scalar operand (left to itself the compiler distributes the shift over j = lane - i * n: two shifts and an add3).
+__device__ __forceinline__ uint2 lds_entry(uint32_t base, uint32_t j)
+{
+    typedef const u32x2_t __attribute__((address_space(3)))* lds_pair_ptr;
+    uint32_t a;
+    asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(a) : "v"(j), "s"(base));
+    const u32x2_t v = *(lds_pair_ptr)(uintptr_t)a;
+    return make_uint2(v.x, v.y);
+}
+// popcount(x) + acc as ONE instruction (left to itself the compiler splits the sum when it feeds an address: two shifts and an add3)
+__device__ __forceinline__ uint32_t bcnt_add(uint32_t x, uint32_t acc)
+{
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+    return r;
+}
+
+// One step: the H-symbol node of every 16-lane slot.  ca, cb (H = 3: and ci) = this lane's columns of the slot's window, th = the
+// node's thresholds (lane constants advanced by the caller's wave-uniform offsets), list = the LDS byte address of the node's list
+// of the slot's window (a lane constant); vmask = the lanes whose slot holds a node of a window of the tile; sh16 = 16 * slot,
+// lt16 = the bits below l16, lt16w = 0xFFFF | lt16 << 16; code16 = l16 * cmul.  Sub-step i's survivors follow sub-step i-1's in the list (ascending code order).
+// The slot's 16-bit field of a ballot is m >> sh16; two sub-steps' fields are packed into one word (v_perm), so that the four
+// sub-steps of a 3-symbol node take two field counts and four rank counts, each with its base in the count's accumulate operand.
+// From code that runs with ALL lanes enabled (the stores write exec).
 template <int H>
-__device__ __forceinline__ void quad_step(const float* cols, uint32_t base, bool valid, uint64_t vmask, const float* th, uint2* list,
-                                          uint32_t l16, uint32_t slot, uint32_t lt16, uint32_t code16, uint32_t cmul, uint32_t& count)
+__device__ __forceinline__ void quad_step(const float* ca, const float* cb, const float* ci, uint64_t vmask, const float* th, uint32_t list,
+                                          uint32_t sh16, uint32_t lt16, uint32_t lt16w, uint32_t code16, uint32_t cmul, uint32_t& count)
 {
     // count: survivors of this lane's slot (the node's list length)
     const float e = th[0];
     if constexpr (H == 2) {
-        const float sl = cols[base + (l16 >> 2)], sr = cols[base + 4 + (l16 & 3u)];
+        const float sl = ca[0], sr = cb[0];
         const float s = sl + sr;                                                   // pk_compute.cpp:90
         const bool c1 = sl > th[1], c2 = sr > th[2], c3 = s > e;                   // as_column x2, :91
-        const bool pass = valid & c1 & c2 & c3;
         const uint64_t m = vmask & ballot64(c1) & ballot64(c2) & ballot64(c3);     // (ballots of the single compares: no VALU)
-        const uint32_t x = (uint32_t)(m >> (16u * slot));
-        const uint32_t pos = (uint32_t)__popc(x & lt16);
-        if (pass) list[pos] = make_uint2(code16, __float_as_uint(s));
+        const uint32_t x = (uint32_t)(m >> sh16);
+        lds_put8_lanes(lshl3_add((uint32_t)__popc(x & lt16), list), code16, __float_as_uint(s), m);
         count = (uint32_t)__popc(x & 0xFFFFu);
     } else {
-        const float sj = cols[base + 4 + (l16 >> 2)], sl2 = cols[base + 8 + (l16 & 3u)];
+        const float sj = ca[0], sl2 = cb[0];
         const float s2 = sj + sl2;                                                 // the inner pair (J+1, J+2)
         const bool d1 = sj > th[3], d2 = sl2 > th[4], d3 = s2 > th[2];
-        const bool okp = valid & d1 & d2 & d3;
         const uint64_t mp = vmask & ballot64(d1) & ballot64(d2) & ballot64(d3);
-        uint32_t run = 0;
+        float s[4]; uint64_t m[4]; uint32_t x[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float si = cols[base + i];
-            const float s = si + s2;                                               // :90
-            const bool c1 = si > th[1], c2 = s > e;                                // :91
-            const bool pass = okp & c1 & c2;
-            const uint64_t m = mp & ballot64(c1) & ballot64(c2);
-            const uint32_t x = (uint32_t)(m >> (16u * slot));
-            const uint32_t pos = (uint32_t)__popc(x & lt16) + run;
-            if (pass) list[pos] = make_uint2(__umul24(cmul, (uint32_t)i * 16u) + code16, __float_as_uint(s));
-            run += (uint32_t)__popc(x & 0xFFFFu);
+            const float si = ci[i];
+            s[i] = si + s2;                                                        // :90
+            const bool c1 = si > th[1], c2 = s[i] > e;                             // :91
+            m[i] = mp & ballot64(c1) & ballot64(c2);
+            x[i] = (uint32_t)(m[i] >> sh16);
         }
-        count = run;
+        const uint32_t y01 = __builtin_amdgcn_perm(x[1], x[0], 0x05040100u);       // fields of sub-steps 0 | 1
+        const uint32_t y23 = __builtin_amdgcn_perm(x[3], x[2], 0x05040100u);       //                     2 | 3
+        const uint32_t n01 = (uint32_t)__popc(y01);
+        const uint32_t pos[4] = {(uint32_t)__popc(x[0] & lt16), (uint32_t)__popc(y01 & lt16w), bcnt_add(x[2] & lt16, n01), bcnt_add(y23 & lt16w, n01)};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lds_put8_lanes(lshl3_add(pos[i], list), __umul24(cmul, (uint32_t)i * 16u) + code16, __float_as_uint(s[i]), m[i]);
+        count = bcnt_add(y23, n01);
     }
 }
 
@@ -156,13 +204,6 @@ __device__ __forceinline__ void pool_store(uint2* wave_base, uint32_t byte_off, 
 {
     const unsigned long long data = ((unsigned long long)val.y << 32) | val.x;
     asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(byte_off), "v"(data), "s"(wave_base) : "memory");
-}
-// (x << 3) + y as ONE instruction (left to itself the compiler shares x << 3 with the rarely taken chunk-roll path and adds separately)
-__device__ __forceinline__ uint32_t lshl3_add(uint32_t x, uint32_t y)
-{
-    uint32_t r;
-    asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
 }
 // The same store for the lanes of `mask`, from code that runs with ALL lanes enabled (uniform control flow in full wavefronts):
 // two scalar instructions around the store instead of the compiler's and-saveexec / branch-if-empty / restore sequence --
@@ -409,17 +450,17 @@ __device__ __forceinline__ void store_pair_if_gt(unsigned long long& cursor, uin
 // operations, codes and list order as join_to_list (pk_compute.cpp:90-91; first child ascending, then second child ascending).
 //
 // A half with <= 64 candidates: the single-step form, for one half.
-template <uint32_t MUL>
-__device__ __forceinline__ uint32_t half_join_single(const uint2* A, const uint2* B, uint32_t nb, uint32_t total, float eps, uint2* out,
+// out + OUT_OFF = the LDS byte address of the list.
+template <uint32_t MUL, uint32_t OUT_OFF>
+__device__ __forceinline__ uint32_t half_join_single(const uint2* A, const uint2* B, uint32_t nb, uint32_t total, float eps, uint32_t out,
                                                      uint32_t lane, float lane_h)
 {
     const float rn = __builtin_amdgcn_rcpf((float)nb);                               // (1 ulp: ample for div_small)
     const uint32_t i = div_small(lane_h, rn), j = (uint32_t)(__mul24((int)i, -(int)nb) + (int)lane);
-    const uint2 a = A[i], b = B[j];                                                  // lanes past the candidates read on in LDS: masked below
+    const uint2 a = A[i], b = lds_entry(lds_addr(B), j);                             // lanes past the candidates read on in LDS: masked below
     const float s = __uint_as_float(a.y) + __uint_as_float(b.y);                     // :90
-    const bool v = lane < total, c = s > eps;                                        // :91
-    const uint64_t h = ballot64(v) & ballot64(c);
-    if (v && c) out[mbcnt(h)] = make_uint2(a.x * MUL + b.x, __float_as_uint(s));
+    const uint64_t h = (~0ull >> (64u - total)) & ballot64(s > eps);                 // :91  (1 <= total <= 64: the valid lanes, wave-uniform)
+    lds_put8_lanes<OUT_OFF>(out + (mbcnt(h) << 3), a.x * MUL + b.x, __float_as_uint(s), h);
     return (uint32_t)__popcll(h);
 }
 // A half with > 64 candidates: the final join's scheme.  The second child's list (nb <= 64 entries) sits in registers, one entry
@@ -505,6 +546,8 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
     uint2* child = scratch_all + (size_t)wave * WS;                // [WPW][CW]
     uint2* lp = child + WPW * Q::CW;                               // L list (codes already multiplied by mulR)
     uint2* rp = lp + CAPL;                                         // R list
+    constexpr uint32_t LP_OFF = WPW * Q::CW * 8u, RP_OFF = LP_OFF + CAPL * 8u;   // lp, rp in bytes behind child_a, for the compacting stores
+    const uint32_t child_a = lds_addr(child);
     using Appender = std::conditional_t<ROWLANE, LaneAppender<NB, CH>, RowAppender<NB, CH, CL::PAIR_BYTES>>;
     Appender app{p, state_all + (size_t)wave * NB, g};
     app.init(blockIdx.x * NW + wave);
@@ -512,36 +555,54 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
 
     // lane roles: slot = lane / 16 = (window half, node slot of the step), 16 candidates per slot
     const uint32_t l16 = lane & 15u, slot = lane >> 4, half = ONEWIN ? 0u : lane >> 5, sb = slot & 1u;
-    const uint32_t lt16 = (1u << l16) - 1u;
+    const uint32_t lt16 = (1u << l16) - 1u, lt16w = 0xFFFFu | (lt16 << 16), sh16 = slot * 16u;
     const float lane_h = (float)lane + 0.5f;
     const float eps = p.eps;
     constexpr bool count_only = COUNT_ONLY;
-    // per step: the node this lane's slot evaluates
-    uint32_t st_j4[NST], st_th[NST], st_off[NST], st_cmul[NST], st_code[NST];
-    bool st_on[NST];
+    // Per step: the node this lane's slot evaluates, as lane constants fixed once per kernel -- the addresses of its columns, its
+    // thresholds and its list for the wavefront's FIRST window pair of a tile (st_ca, st_cb, st_ci, st_thp, st_list; the pair loop
+    // adds wave-uniform offsets, one instruction per address) -- and the lanes whose slot holds a node at all (ST_ON).
+    // Three steps (k = 9): st_cb is st_ca + cb_ca, one more add per step, for two registers less -- with all of them held the kernel
+    // needs 75 VGPRs, and a seventh wavefront per SIMD, which its LDS admits, needs 72.
+    constexpr bool CB_FROM_CA = NST > 2;
+    const uint32_t cb_ca = 4u + (l16 & 3u) - (l16 >> 2);           // the same for 2- and 3-symbol nodes
+    const float *st_ca[NST], *st_cb[NST], *st_ci[NST], *st_thp[NST];
+    uint32_t st_list[NST];
+    uint32_t st_cmul[NST], st_code[NST];
+    uint64_t ST_ON[NST];
 #pragma unroll
     for (int s = 0; s < NST; ++s) {
         constexpr QuadNode none{0, 2, 0, 0, 0, 1u};
+        uint32_t j4, tho, off;
         if constexpr (ONEWIN) {
             QuadNode nd = none;
-            bool on = false;
+            uint64_t on = 0;
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) {
                 const int n = Q::step1_node(s, sl);
-                if (n >= 0 && slot == (uint32_t)sl) { nd = Q::node(n); on = true; }
+                if (n >= 0) on |= 0xFFFFull << (16 * sl);
+                if (n >= 0 && slot == (uint32_t)sl) nd = Q::node(n);
             }
-            st_j4[s] = (uint32_t)nd.J * 4u; st_th[s] = (uint32_t)nd.TH; st_off[s] = (uint32_t)nd.OFF; st_cmul[s] = nd.CMUL;
-            st_code[s] = l16 * st_cmul[s]; st_on[s] = on;
+            j4 = (uint32_t)nd.J * 4u; tho = (uint32_t)nd.TH; off = (uint32_t)nd.OFF; st_cmul[s] = nd.CMUL;
+            ST_ON[s] = on;
         } else {
             const QuadStep qs = Q::step(s);
             const QuadNode na = Q::node(qs.A), nb = qs.B >= 0 ? Q::node(qs.B) : none;
-            st_j4[s] = sb ? (uint32_t)nb.J * 4u : (uint32_t)na.J * 4u;
-            st_th[s] = sb ? (uint32_t)nb.TH : (uint32_t)na.TH;
-            st_off[s] = (sb ? (uint32_t)nb.OFF : (uint32_t)na.OFF) + half * Q::CW;
+            j4 = sb ? (uint32_t)nb.J * 4u : (uint32_t)na.J * 4u;
+            tho = sb ? (uint32_t)nb.TH : (uint32_t)na.TH;
+            off = (sb ? (uint32_t)nb.OFF : (uint32_t)na.OFF) + half * Q::CW;
             st_cmul[s] = sb ? nb.CMUL : na.CMUL;
-            st_code[s] = l16 * st_cmul[s];
-            st_on[s] = sb ? qs.B >= 0 : true;
+            ST_ON[s] = qs.B >= 0 ? ~0ull : 0x0000FFFF0000FFFFull;
         }
+        st_code[s] = l16 * st_cmul[s];
+        const int H = ONEWIN ? Q::step1_h(s) : Q::step(s < Q::NSTEPS ? s : 0).H;
+        const float* c0 = cols + (wave * WPW + half) * 4u + j4;                 // the node's first column of this lane's window
+        st_ci[s] = c0;
+        st_ca[s] = c0 + (H == 2 ? 0u : 4u) + (l16 >> 2);
+        st_cb[s] = c0 + (H == 2 ? 4u : 8u) + (l16 & 3u);
+        st_thp[s] = thr + (wave * WPW + half) * (uint32_t)Q::TH_F + tho;
+        st_list[s] = child_a + off * 8u;
+        asm("" : "+v"(st_list[s]));                                             // (one VGPR: base and offset are not added again per store)
     }
 
     // Tiles: a fixed range per workgroup, or -- p.tile_next -- drawn one at a time from the group's counter, so that the group's S
@@ -586,21 +647,21 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
         __syncthreads();
 
         const uint32_t npair = (nw + WPW - 1) / WPW;
-        const float* thw = thr + __umul24(wave * WPW + half, (uint32_t)Q::TH_F);    // this lane's window's thresholds: advanced, not recomputed
-        for (uint32_t pr = wave; pr < npair; pr += NW, thw += WPW * NW * Q::TH_F) {
+        for (uint32_t pr = wave; pr < npair; pr += NW) {
             const uint32_t wq = pr * WPW;
-            const uint32_t wl = wq + half;                                       // this lane's window
-            const bool wvalid = wl < nw;
+            const uint32_t wo = wq - wave * WPW;                                 // windows past the wavefront's first pair (wave-uniform)
+            // the lanes whose window lies inside the tile: all, or -- the tile's last, single window -- those of the pair's first half
+            const uint64_t wmask = ONEWIN || wq + 1 < nw ? ~0ull : 0xFFFFFFFFull;
             uint32_t counts[3] = {0, 0, 0};                                      // per step: list length of this lane's slot
             wave_lds_sync();                                                     // the previous pair's lists are consumed
             auto run_step = [&](auto S) {
                 constexpr int s = decltype(S)::value;
                 if constexpr (s < NST) {
-                    const bool valid = wvalid && st_on[s];
-                    const uint64_t vmask = ballot64(valid);
-                    const uint32_t base = wl * 4 + st_j4[s];
                     constexpr int H = ONEWIN ? Q::step1_h(s) : Q::step(s < Q::NSTEPS ? s : 0).H;
-                    quad_step<H>(cols, base, valid, vmask, thw + st_th[s], child + st_off[s], l16, slot, lt16, st_code[s], st_cmul[s], counts[s]);
+                    const uint32_t co = wo * 4u, to = wo * (uint32_t)Q::TH_F;
+                    const float* ca = st_ca[s] + co;
+                    quad_step<H>(ca, CB_FROM_CA ? ca + cb_ca : st_cb[s] + co, st_ci[s] + co, wmask & ST_ON[s], st_thp[s] + to, st_list[s], sh16, lt16, lt16w,
+                                 st_code[s], st_cmul[s], counts[s]);
                 }
             };
             run_step(std::integral_constant<int, 0>{});
@@ -649,24 +710,23 @@ __global__ __launch_bounds__(NW * 64) void score_quad_kernel(StreamParams p)
                     const uint32_t il = div_small(lane_h, rnl), jl = (uint32_t)(__mul24((int)il, -(int)nlb) + (int)lane);
                     const uint32_t ir = div_small(lane_h, rnr), jr = (uint32_t)(__mul24((int)ir, -(int)nrb) + (int)lane);
                     // lanes past a half's candidates read the entries that follow in LDS and are masked out of the ballots
-                    const uint2 a0 = la[il], b0 = lb[jl], a1 = ra[ir], b1 = rb[jr];
+                    const uint2 a0 = la[il], b0 = lds_entry(lds_addr(lb), jl), a1 = ra[ir], b1 = lds_entry(lds_addr(rb), jr);
                     const float s0 = __uint_as_float(a0.y) + __uint_as_float(b0.y);          // :90
                     const float s1 = __uint_as_float(a1.y) + __uint_as_float(b1.y);
-                    const bool v0 = lane < tl, v1 = lane < tr, c0 = s0 > eps_l, c1 = s1 > eps_r;    // :91
-                    const bool p0 = v0 && c0, p1 = v1 && c1;
-                    const uint64_t h0 = ballot64(v0) & ballot64(c0), h1 = ballot64(v1) & ballot64(c1);
-                    if (p0) lp[mbcnt(h0)] = make_uint2(a0.x * (Q::FLB * mulR) + b0.x, __float_as_uint(s0));   // lb codes carry mulR
-                    if (p1) rp[mbcnt(h1)] = make_uint2(a1.x * Q::FRB + b1.x, __float_as_uint(s1));
+                    // :91  (1 <= tl, tr <= 64: a half's valid lanes are the wave-uniform (1 << t) - 1, built on the scalar side)
+                    const uint64_t h0 = (~0ull >> (64u - tl)) & ballot64(s0 > eps_l), h1 = (~0ull >> (64u - tr)) & ballot64(s1 > eps_r);
+                    lds_put8_lanes<LP_OFF>(child_a + (mbcnt(h0) << 3), a0.x * (Q::FLB * mulR) + b0.x, __float_as_uint(s0), h0);   // lb codes carry mulR
+                    lds_put8_lanes<RP_OFF>(child_a + (mbcnt(h1) << 3), a1.x * Q::FRB + b1.x, __float_as_uint(s1), h1);
                     nL = (uint32_t)__popcll(h0); nR = (uint32_t)__popcll(h1);
                 } else {
                     // (the list lengths are wave-uniform by construction; without the readfirstlane the branches below count as
                     //  divergent, and every value carried around this loop -- the appender's state -- is then held in VGPRs)
                     if constexpr (!ROWLANE) {
                         // each half by its own size (half_join_single / half_join_rows above); an empty L: R is not built
-                        nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tl <= 64 ? half_join_single<Q::FLB * mulR>(la, lb, nlb, tl, eps_l, lp, lane, lane_h)
+                        nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tl <= 64 ? half_join_single<Q::FLB * mulR, LP_OFF>(la, lb, nlb, tl, eps_l, child_a, lane, lane_h)
                                                                                        : half_join_rows<Q::FLB * mulR>(la, nla, lb, nlb, eps_l, lp, CAPL, lane, lane_h)));
                         nR = nL == LIST_OVERFLOW || nL == 0 ? nL
-                           : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tr <= 64 ? half_join_single<Q::FRB>(ra, rb, nrb, tr, eps_r, rp, lane, lane_h)
+                           : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tr <= 64 ? half_join_single<Q::FRB, RP_OFF>(ra, rb, nrb, tr, eps_r, child_a, lane, lane_h)
                                                                                       : half_join_rows<Q::FRB>(ra, nra, rb, nrb, eps_r, rp, CAPR, lane, lane_h)));
                     } else {
                     if (!keep_l)
