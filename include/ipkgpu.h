@@ -574,13 +574,62 @@ int ipkgpu_db_file_check(ipkgpu_db_file* f, uint64_t* n_records, uint64_t* n_ent
  * is IPKGPU_ERR_INVALID before the first of them is launched.  Also IPKGPU_ERR_INVALID: a key in two records, more than
  * 2^32 - 1 records, a record of 2^32 entries or more.  Device memory: the image (the body's bytes, freed before the call returns)
  * plus the database plus 44 bytes per k-mer of workspace and the sort's own, all counted by ipkgpu_mem_stats and held to "device_budget_bytes";
- * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded in pieces. */
+ * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded in pieces
+ * (ipkgpu_db_load_select below loads a prefix of it). */
 int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out);
 /* The head of the file a database was loaded from (owned by the database); NULL for databases that were not loaded. */
 const ipkgpu_db_file* ipkgpu_db_header_of(const ipkgpu_db* d);
-/* The last ipkgpu_db_load of this context: 0 = seconds in all, 1 = file reads, 2 = the host's walk, 3 = waiting for the device;
- * 4 = db_unpack_heads_kernel ms, 5 = db_unpack_entries_kernel ms, 6 = all device work behind the last copy, ms. */
+/* The last ipkgpu_db_load or ipkgpu_db_load_select of this context: 0 = seconds in all, 1 = file reads, 2 = the host's walk,
+ * 3 = waiting for the device; 4 = db_unpack_heads_kernel ms, 5 = db_unpack_entries_kernel ms, 6 = all device work behind the last
+ * copy, ms; 7 = the bytes of the file's body the call touched: the whole body for a full load; for a prefix load the prefix rounded
+ * up to a load chunk (the extent of the walk -- the copy then reads exactly the prefix, inside that extent). */
 double ipkgpu_db_load_time(const ipkgpu_ctx* ctx, int which);
+
+/* ---- selection: the consumer of the filter order -- the most informative fraction mu of a database, at a raised threshold ------------
+ * The filter stages put the k-mers of a database (and the records of its file) into filter order so that a consumer can take only
+ * the first of them, and can raise the score threshold without a rebuild.  THE DEFINITION BELOW IS THIS LIBRARY'S OWN AND UNPINNED:
+ * the reference's reader, i2l::load(file, mu, omega), is un-vendored and could not be read, so what it does with mu and omega beyond
+ * what their names say was not checked (as for the ambiguity expansion of ipkgpu_db_place_opts).
+ *
+ * Source database D: keys ascending, key_offsets, entries, positions if it has them, filter values (float and double) and order,
+ * keys[order[i]] being the i-th record.  For keep_kmers = M and min_log_score = t the selection V is:
+ *   1. candidates  the records i < min(M, num_keys) of D's order, i.e. the keys order[i].  M larger than num_keys behaves as num_keys.
+ *   2. entries     of a candidate key, in D's order, those with score > t: a binary32 comparison, strict -- the build's own rule
+ *                  (an entry is stored iff its score exceeds the threshold).  A NaN score fails it; t = -inf keeps every entry (of a
+ *                  score that is neither NaN nor -inf: no build stores those); positions travel with their entries.
+ *   3. keys        a candidate left without an entry is dropped, like every non-candidate.  M counts records BEFORE step 2, as a
+ *                  reader that stops after M records counts them.
+ *   4. arrays      V's keys ascend; its filter values are D's bit for bit, float and double (nothing is recomputed); V's order is
+ *                  the surviving records in D's order, renumbered to V's key indices.
+ *   5. head        ipkgpu_db_header_of(V): for a loaded D a copy of D's head with the two totals replaced by V's -- omega stays
+ *                  as it is, for the call takes t and no omega; NULL when D was not loaded.
+ * IPKGPU_ERR_INVALID: a NaN t, a D without filter arrays (built and never filtered), NULL arguments, a D of another context.
+ * An empty V (M = 0, t = +inf, ...) is IPKGPU_OK with num_keys 0: every accessor, ipkgpu_db_write and placement take it (every query
+ * then has no placement).  V is an ordinary database, independent of D; D is only read and stays valid.
+ * All device work (kernels_dbselect.hpp): candidate flags scattered from the order, a keep flag per entry -- by entry ranges, so one
+ * key of 5000 entries costs what 5000 keys of one entry cost --, exclusive scans of the flags, then compacting copies.  Output places
+ * come from the scans alone (no atomics): the same bits on every run.  Device memory: V, plus 12 bytes per entry and 12 per key of D
+ * and 12 per record i < M of workspace and the scans' own, counted by ipkgpu_mem_stats and held to "device_budget_bytes"; what does
+ * not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  ipkgpu_db_select_time_ms: device time of the context's last selection. */
+int ipkgpu_db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float min_log_score, ipkgpu_db** out);
+double ipkgpu_db_select_time_ms(const ipkgpu_ctx* ctx);
+/* mu -> M: min(n_kmers, (uint64_t)ceil((double)mu * (double)n_kmers)), in binary64.  Callers refuse mu outside [0, 1] and NaN
+ * (here: mu <= 0 and NaN give 0, mu >= 1 gives n_kmers).  Host only. */
+uint64_t ipkgpu_db_mu_kmers(double mu, uint64_t n_kmers);
+/* ipkgpu_db_select(ipkgpu_db_load(path), keep_kmers, min_log_score) bit for bit in every array, the order included -- reading and
+ * walking only the prefix of the file's body that holds its first min(keep_kmers, header total) records (the file IS in filter
+ * order).  File bytes read, and the device image, are at most that prefix rounded up to one load chunk ("db_load_chunk_bytes");
+ * ipkgpu_db_load_time(ctx, 7) tells that rounded-up figure.  The head is validated as by ipkgpu_db_load; the walk stops at keep_kmers records
+ * and every one of them must end inside the file (else IPKGPU_ERR_INVALID naming the record).  That the walk ends at the end of the
+ * file, and that its totals are the header's, cannot be checked on a prefix: both checks are made only when keep_kmers >= the
+ * header's total -- the call is then a full ipkgpu_db_load followed by the selection -- and DAMAGE BEHIND THE PREFIX IS NOT SEEN.
+ * The prefix walk reads the count fields through a read-only mapping of the file (its length is known only at the walk's end, and the
+ * image is allocated at exactly that length before the prefix is read through the pinned buffers).  The file's size is checked against
+ * the one the head was parsed at before it is mapped; a file that ANOTHER PROCESS TRUNCATES DURING THE CALL, or an I/O error under the
+ * mapping, is a SIGBUS to this process -- not the IPKGPU_ERR_INVALID the full load's reads make of the same events.  Do not load a
+ * prefix of a file that is being rewritten.
+ * A file larger than device memory loads this way for every keep_kmers whose prefix (plus its database and the selection) fits. */
+int ipkgpu_db_load_select(ipkgpu_ctx* ctx, const char* path, uint64_t keep_kmers, float min_log_score, ipkgpu_db** out);
 
 /* ipkdiff's comparison of two databases of one context (tools/src/diff.cpp:210-295), on the device (kernels_dbdiff.hpp). */
 typedef struct ipkgpu_db_diff_counts {

@@ -443,6 +443,46 @@ def placement_lines(names, res, keep_factor, with_strand=False):
     return lines
 
 
+def _check_selection(db_path, mu, omega):
+    """Refuses, with a message, a --mu outside [0, 1] and an --omega below the file's (entries under the build's threshold are not in
+    the file, so a lower omega cannot be served)."""
+    from ipk_amd import dbfile
+    if mu is not None and not 0.0 <= mu <= 1.0:
+        raise click.UsageError(f"--mu must be in [0, 1], not {mu}")
+    if omega is not None:
+        file_omega = dbfile.file_info(db_path)["omega"]
+        if not np.float32(omega) >= np.float32(file_omega):          # binary32, as the file stores it: the build's own --omega is not below it
+            raise click.UsageError(f"--omega {_g(omega)} is below the file's omega {_g(file_omega)}: entries under the build's threshold "
+                                   "are not in the file")
+
+
+@ipk.command()
+@click.option("-i", "--input", "db_path", required=True, type=click.Path(exists=True, dir_okay=False), help="database file (of this engine's builds)")
+@click.option("-o", "--output", required=True, help="the selection's database file")
+@click.option("--mu", type=float, default=None, help="keep the first fraction MU of the file's k-mers in filter order [all]")
+@click.option("--omega", type=float, default=None, help="keep the entries above this omega's threshold; becomes the output's omega [the file's]")
+@click.option("--device", type=int, default=0, show_default=True, help="GPU index")
+def subset(db_path, output, mu, omega, device):
+    """Writes a selection of a database file as a database file: the first fraction --mu of its k-mers in filter order, of those
+    the entries above --omega's threshold (ipkgpu_db_load_select; the definition is in include/ipkgpu.h and is this engine's own --
+    the reference's load(file, mu, omega) could not be read).  The file is loaded as far as the selection needs, selected on the GPU
+    and written by the device writer; the head is the input's with the new totals and, if given, the new omega."""
+    import ipk_amd
+    from ipk_amd import dbfile
+    _check_selection(db_path, mu, omega)
+    eng = ipk_amd.Engine(device)
+    try:
+        d = eng.load_db(db_path, mu=1.0 if mu is None else mu, omega=omega)
+        head = dbfile.header_args(d.header)
+        if omega is not None:
+            head["omega"] = omega
+        dbfile.write_db_device(eng, d, output, **head)
+        click.echo(f"Output: {output} ({d.num_keys} k-mers, {d.num_entries} entries)")
+        d.free()
+    finally:
+        eng.close()
+
+
 @ipk.command()
 @click.option("-i", "--input", "db_path", required=True, type=click.Path(exists=True, dir_okay=False), help="database file (of this engine's builds)")
 @click.option("-q", "--queries", required=True, type=click.Path(exists=True, dir_okay=False), help="query sequences (FASTA)")
@@ -453,21 +493,27 @@ def placement_lines(names, res, keep_factor, with_strand=False):
               help="expand a k-mer with one ambiguous symbol (N, R, Y, ...; amino acids B, Z, J, X) into its resolutions")
 @click.option("--strands", type=click.Choice(["given", "both"]), default="given", show_default=True,
               help="both: place the reverse complement too (DNA) and keep the better strand; adds a seventh column, + or -")
+@click.option("--mu", type=float, default=None, help="place on the first fraction MU of the file's k-mers in filter order only [all]")
+@click.option("--omega", type=float, default=None, help="place at this omega: entries at or below its threshold are left out [the file's]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, device):
+def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, device):
     """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
     branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
 
     One TSV line per kept placement: query, branch, score, count, n_kmers, lwr -- branch is the stored post-order id (what `dump`
     prints for a file without a tree), score the log10 score with the threshold standing in for the query's k-mers the branch does
     not score, count those it does, n_kmers the query's valid k-mers.  By default the given strand only, and symbols outside the
-    alphabet (N, X, ...) end a k-mer; --expand-ambiguous and --strands both change that (ipkgpu_db_place_opts in include/ipkgpu.h)."""
+    alphabet (N, X, ...) end a k-mer; --expand-ambiguous and --strands both change that (ipkgpu_db_place_opts in include/ipkgpu.h).
+
+    --mu / --omega load a selection of the file (ipkgpu_db_load_select: only the prefix of the file that holds the first k-mers is
+    read) and place on it, at --omega's threshold; what `subset` with the same options writes places alike."""
     import ipk_amd
+    _check_selection(db_path, mu, omega)
     with open(queries) as fh:
         recs = read_fasta(fh.read())
     eng = ipk_amd.Engine(device)
     try:
-        d = eng.load_db(db_path)
+        d = eng.load_db(db_path, mu=mu, omega=omega)
         res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
         text = "".join(line + "\n" for line in placement_lines([n for n, _ in recs], res, keep_factor, strands == "both"))
         if output:

@@ -5,6 +5,7 @@
 // ipkgpu_db_file_check) -- the only serial part, and the only place a number of the file is believed.  A file the walk refuses
 // launches nothing.  Then kernels_dbload.hpp: heads in file order, a sort of (key, record) with the filter stage's radix sort,
 // a scan of the counts in key order, entries by entry ranges.  The image is freed before the call returns.
+// db_load_records is that load for the first M records of the file as well (ipkgpu_db_load_select, db_select.hpp).
 // ipkgpu_db_diff: kernels_dbdiff.hpp -- join, count pass, scan, write pass.
 #pragma once
 
@@ -15,7 +16,34 @@ double ipkgpu_db_load_time(const ipkgpu_ctx* ctx, int which) { return ctx && whi
 double ipkgpu_db_diff_time_ms(const ipkgpu_ctx* ctx) { return ctx ? ctx->t_diff_ms : 0; }
 uint32_t ipkgpu_db_diff_chunk(void) { return DB_DIFF_CHUNK; }
 
-int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out)
+}  // extern "C"
+
+namespace {
+
+// The seven device arrays of a database of n keys and ne entries (each at least one element, as every producer allocates them).
+int db_alloc_arrays(ipkgpu_ctx* ctx, ipkgpu_db* db, uint64_t n, uint64_t ne, bool positioned)
+{
+    db->n_keys = n; db->n_entries = ne;
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_keys, std::max<uint64_t>(n, 1) * 4));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_key_off, (n + 1) * 8));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_entries, std::max<uint64_t>(ne, 1) * 8));
+    if (positioned) HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_positions, std::max<uint64_t>(ne, 1) * 4));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv64, std::max<uint64_t>(n, 1) * 8));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv32, std::max<uint64_t>(n, 1) * 4));
+    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_order, std::max<uint64_t>(n, 1) * 4));
+    return IPKGPU_OK;
+}
+
+// The load behind ipkgpu_db_load (keep_records = all) and ipkgpu_db_load_select: the first min(keep_records, header total) records of
+// the file as a database.  keep_records >= the header's total is the whole file, read and checked as ever.  Fewer: only the prefix of
+// the body that holds them is touched.  How long that prefix is shows only when the walk has seen its last record, so the walk goes
+// first, over a read-only mapping of the file and chunk by chunk; then an image of exactly the prefix' bytes is allocated and the
+// prefix streamed into it through the same pinned buffers (from the page cache the walk has just filled).  The walk stops at
+// keep_records records, each of which ends inside the file; that it ends at the end of the file with the header's totals cannot be
+// asked of a prefix, and the head kept with the database carries the prefix' own totals.  (A mapping, not reads: a file truncated by
+// another process behind the size check below, or an I/O error, is a SIGBUS here where the full load's fread gives IPKGPU_ERR_INVALID;
+// include/ipkgpu.h says so.)  t_load[7] for a prefix is the walk's extent, the prefix rounded up to a chunk.
+int db_load_records(ipkgpu_ctx* ctx, const char* path, uint64_t keep_records, ipkgpu_db** out)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (out) *out = nullptr;
@@ -25,39 +53,73 @@ int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out)
     ipkgpu_db_file* file = nullptr;
     if (const int rc = ipkgpu_db_file_open(path, &file)) return fail(ctx, rc, "%s", ipkgpu_db_file_last_error());
     struct FileGuard { ipkgpu_db_file* f; ~FileGuard() { ipkgpu_db_file_close(f); } } fguard{file};
-    const ipkfmt::Head& hd = file->head;
-    const uint64_t n = hd.total_kmers, ne = hd.total_entries, body = file->body_bytes();
+    ipkfmt::Head& hd = file->head;
+    const bool whole = keep_records >= hd.total_kmers;
+    uint64_t n = hd.total_kmers, ne = hd.total_entries;
+    const uint64_t body = file->body_bytes();
     const bool positioned = hd.positions_loaded;
     if (n > 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %llu k-mers: a database holds at most 2^32 - 1 (its order is 32-bit)", path, (unsigned long long)n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-    // the image of the body (+16: the positioned entries are read as aligned dwords, the last one two bytes past its end)
+    // the image of the body or of its prefix (+16: the positioned entries are read as aligned dwords, the last one two bytes past its end)
     unsigned char* image = nullptr;
-    const size_t image_bytes = (size_t)body + 16;
-    struct ImageGuard { ipkgpu_ctx* c; unsigned char*& p; size_t bytes;
+    size_t image_bytes = 0;
+    struct ImageGuard { ipkgpu_ctx* c; unsigned char*& p; size_t& bytes;
         ~ImageGuard() { if (p) { (void)hipStreamSynchronize(c->stream); (void)dev_free(c, p, bytes); p = nullptr; } (void)hipGetLastError(); } } iguard{ctx, image, image_bytes};
-    {
+    auto alloc_image = [&](uint64_t bytes) -> int {
+        image_bytes = (size_t)bytes + 16;
         const hipError_t e = dev_malloc(ctx, (void**)&image, image_bytes);
         if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? IPKGPU_ERR_NOMEM : IPKGPU_ERR_HIP, "%s: no room for the image of the file's body (%llu bytes): %s",
-                                         path, (unsigned long long)body, hipGetErrorString(e));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(image + body, 0, 16, ctx->stream));
-
-    // file -> pinned buffer -> image, the host walking every chunk before it leaves
+                                         path, (unsigned long long)bytes, hipGetErrorString(e));
+        HIP_TRY(ctx, hipMemsetAsync(image + bytes, 0, 16, ctx->stream));
+        return IPKGPU_OK;
+    };
     const uint64_t chunk = std::min<uint64_t>(ctx->opt_load_chunk > 0 ? (uint64_t)ctx->opt_load_chunk : SPILL_STAGE, SPILL_STAGE);
-    RC_TRY(spill_stage(ctx, (size_t)std::min<uint64_t>(chunk, std::max<uint64_t>(body, 1))));
     ipkfmt::RecordWalker walk;
-    walk.begin(hd.body_at, body, positioned, n);
+    walk.begin(hd.body_at, body, positioned, n, whole ? ~(uint64_t)0 : keep_records);
     double t_read = 0, t_walk = 0, t_wait = 0;
+    uint64_t bytes_read = 0;
     {
         FILE* fh = fopen(path, "rb");
         if (!fh) return fail(ctx, IPKGPU_ERR_INVALID, "cannot open %s", path);
         struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fh};
         setvbuf(fh, nullptr, _IONBF, 0);
+        uint64_t extent = body;                                              // the body bytes that go to the device
+        if (!whole) {
+            // the walk of the prefix, ahead of everything: over a read-only mapping of the file, chunk by chunk, until the last record
+            // asked for is known -- only then is the prefix' length known, and the image allocated at exactly that
+            struct stat st;
+            if (fstat(fileno(fh), &st) != 0 || (uint64_t)st.st_size != file->file_bytes) return fail(ctx, IPKGPU_ERR_INVALID, "%s: the file changed since it was opened", path);
+            const auto t0 = std::chrono::steady_clock::now();
+            uint64_t lo = 0;
+            if (body && keep_records) {
+                void* map = mmap(nullptr, (size_t)file->file_bytes, PROT_READ, MAP_PRIVATE, fileno(fh), 0);
+                if (map == MAP_FAILED) return fail(ctx, IPKGPU_ERR_INVALID, "%s: cannot map the file", path);
+                struct Unmap { void* p; size_t n; ~Unmap() { munmap(p, n); } } unmap{map, (size_t)file->file_bytes};
+                (void)madvise(map, (size_t)file->file_bytes, MADV_SEQUENTIAL);
+                const uint8_t* base = static_cast<const uint8_t*>(map) + hd.body_at;
+                for (; lo < body && !(walk.done() && lo >= walk.pos); lo += chunk)
+                    if (!walk.feed(base + lo, lo, std::min(body, lo + chunk))) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %s", path, walk.error.c_str());
+            }
+            t_walk += since(t0);
+            bytes_read = std::min(body, lo);                                 // (the chunks the walk touched; the copy below reads inside them)
+            if (!walk.done() || walk.pos > bytes_read)
+                return fail(ctx, IPKGPU_ERR_INVALID, "%s: the file ends before record %llu of the first %llu has ended", path,
+                            (unsigned long long)walk.starts.size(), (unsigned long long)keep_records);
+            extent = walk.pos;
+            n = walk.starts.size(); ne = walk.n_entries;
+            hd.total_kmers = n; hd.total_entries = ne;
+            file->file_bytes = hd.body_at + extent;
+        } else {
+            bytes_read = body;
+        }
+        RC_TRY(alloc_image(extent));
         if (fseeko(fh, (off_t)hd.body_at, SEEK_SET) != 0) return fail(ctx, IPKGPU_ERR_INVALID, "%s: seek failed", path);
+        // file -> pinned buffer -> image, the next read under the previous copy; the whole file's walk sees every chunk before it leaves
+        RC_TRY(spill_stage(ctx, (size_t)std::min<uint64_t>(chunk, std::max<uint64_t>(extent, 1))));
         uint64_t j = 0;
-        for (uint64_t lo = 0; lo < body; lo += chunk, ++j) {
-            const uint64_t hi = std::min(body, lo + chunk);
+        for (uint64_t lo = 0; lo < extent; lo += chunk, ++j) {
+            const uint64_t hi = std::min(extent, lo + chunk);
             const int b = (int)(j & 1);
             auto t0 = std::chrono::steady_clock::now();
             HIP_TRY(ctx, hipEventSynchronize(ctx->ev_spill[b]));        // (the copy out of this buffer two chunks ago; at once on a fresh event)
@@ -65,13 +127,13 @@ int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out)
             uint8_t* src = static_cast<uint8_t*>(ctx->h_spill[b]);
             if (fread(src, 1, (size_t)(hi - lo), fh) != hi - lo) return fail(ctx, IPKGPU_ERR_INVALID, "%s: read failed", path);
             t_read += since(t0); t0 = std::chrono::steady_clock::now();
-            if (!walk.feed(src, lo, hi)) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %s", path, walk.error.c_str());
+            if (whole && !walk.feed(src, lo, hi)) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %s", path, walk.error.c_str());
             t_walk += since(t0);
             HIP_TRY(ctx, hipMemcpyAsync(image + lo, src, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipEventRecord(ctx->ev_spill[b], ctx->stream));
         }
     }
-    if (!walk.finish(n, ne)) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %s", path, walk.error.c_str());
+    if (whole && !walk.finish(n, ne)) return fail(ctx, IPKGPU_ERR_INVALID, "%s: %s", path, walk.error.c_str());
     if (walk.max_count > 0xFFFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "%s: a k-mer with 2^32 entries or more", path);
     if ((ne + DB_UNPACK_TILE - 1) / DB_UNPACK_TILE > 0x7FFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "%s: too many entries for one launch", path);
     file->walked = true; file->n_records = n; file->n_entries = ne; file->max_count = walk.max_count;
@@ -81,14 +143,7 @@ int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out)
     if (!db) return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory");
     db->ctx = ctx;
     struct Guard { ipkgpu_db* r; ~Guard() { if (r) ipkgpu_db_free(r); } } guard{db};
-    db->n_keys = n; db->n_entries = ne;
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_keys, std::max<uint64_t>(n, 1) * 4));
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_key_off, (n + 1) * 8));
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_entries, std::max<uint64_t>(ne, 1) * 8));
-    if (positioned) HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_positions, std::max<uint64_t>(ne, 1) * 4));
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv64, std::max<uint64_t>(n, 1) * 8));
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_fv32, std::max<uint64_t>(n, 1) * 4));
-    HIP_TRY(ctx, ctx_alloc(ctx, (void**)&db->d_order, std::max<uint64_t>(n, 1) * 4));
+    RC_TRY(db_alloc_arrays(ctx, db, n, ne, positioned));
     Stopwatch sw(ctx->stream, &ctx->events);
     const int e0 = sw.mark();
     int eh = e0, e1 = e0, e2 = e0, e3 = e0;
@@ -155,12 +210,19 @@ int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out)
     db->t_merge = sw.ms(e0, e3);
     ctx->t_load[1] = t_read; ctx->t_load[2] = t_walk; ctx->t_load[3] = t_wait;
     ctx->t_load[4] = n ? sw.ms(eh, e1) : 0; ctx->t_load[5] = n ? sw.ms(e2, e3) : 0; ctx->t_load[6] = db->t_merge;
+    ctx->t_load[7] = (double)bytes_read;
     db->file = file; fguard.f = nullptr;
     guard.r = nullptr;
     *out = db;
     ctx->t_load[0] = since(t_begin);
     return IPKGPU_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out) { return db_load_records(ctx, path, ~(uint64_t)0, out); }
 
 int ipkgpu_db_diff(ipkgpu_ctx* ctx, const ipkgpu_db* a, const ipkgpu_db* b, double eps, ipkgpu_db_diff_counts* counts,
                    ipkgpu_db_diff_record* records, uint64_t max_records, uint64_t* n_records)

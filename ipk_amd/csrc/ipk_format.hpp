@@ -178,16 +178,19 @@ inline bool read_head(FILE* f, uint64_t& total_kmers, uint64_t& total_entries, b
 // The body's bytes are fed in order, in chunks of any size (a head may straddle two); only the count fields are looked at.  Kept:
 // every record's start (body-relative) and the totals.  A count that would carry its record past the end of the body stops the
 // walk with a message naming the record and its byte offset in the FILE, before anything could index by it.
+// stop_records: the walk of a PREFIX of the file (ipkgpu_db_load_select) -- once that many records are known nothing more is looked
+// at; `pos` is then where the last of them ends, inside the body like every record the walk accepts.
 struct RecordWalker {
-    uint64_t body_at = 0, body_bytes = 0, entry_bytes = ENTRY_BYTES, max_records = ~(uint64_t)0;
+    uint64_t body_at = 0, body_bytes = 0, entry_bytes = ENTRY_BYTES, max_records = ~(uint64_t)0, stop_records = ~(uint64_t)0;
     uint64_t pos = 0;                        // start of the record whose head is being collected
     uint64_t n_entries = 0, max_count = 0;
     std::vector<uint64_t> starts;
     uint8_t carry[RECORD_HEAD_BYTES]; uint32_t carry_n = 0;
     std::string error;
-    void begin(uint64_t body_at_, uint64_t body_bytes_, bool positions, uint64_t max_records_)
+    void begin(uint64_t body_at_, uint64_t body_bytes_, bool positions, uint64_t max_records_, uint64_t stop_records_ = ~(uint64_t)0)
     {
         body_at = body_at_; body_bytes = body_bytes_; entry_bytes = positions ? ENTRY_POS_BYTES : ENTRY_BYTES; max_records = max_records_;
+        stop_records = stop_records_;
         pos = 0; n_entries = 0; max_count = 0; carry_n = 0; starts.clear(); error.clear();
     }
     bool fail_at(const char* what, uint64_t count)
@@ -198,10 +201,11 @@ struct RecordWalker {
         error = b;
         return false;
     }
+    bool done() const { return starts.size() >= stop_records; }
     // body bytes [lo, hi) at `data`; chunks follow each other without gaps
     bool feed(const uint8_t* data, uint64_t lo, uint64_t hi)
     {
-        while (pos + carry_n < hi) {
+        while (pos + carry_n < hi && !done()) {
             const uint64_t at = pos + carry_n;
             const uint32_t take = (uint32_t)std::min<uint64_t>(RECORD_HEAD_BYTES - carry_n, hi - at);
             memcpy(carry + carry_n, data + (at - lo), take);

@@ -42,10 +42,12 @@
 #include "kernels_dbfile.hpp"
 #include "kernels_spill.hpp"
 #include "kernels_dbload.hpp"
+#include "kernels_dbselect.hpp"
 #include "kernels_dbdiff.hpp"
 #include "kernels_place.hpp"
 #include "db_file.hpp"
 #include "spill_format.hpp"
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <chrono>
 
@@ -174,8 +176,9 @@ struct ipkgpu_ctx {
     uint64_t last_entries = 0; uint32_t last_gb = 0;   // the key-major writer's output of the previous batch: the next one's estimate
     double t_write_total = 0, t_write_device = 0, t_write_file = 0;   // last ipkgpu_db_write
     int64_t opt_load_chunk = 0;          // "db_load_chunk_bytes": bytes per pinned buffer of ipkgpu_db_load (0: SPILL_STAGE, the spill blocks')
-    double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
+    double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load / ipkgpu_db_load_select (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
     double t_diff_ms = 0;
+    double t_select_ms = 0;              // device time of the last ipkgpu_db_select (ipkgpu_db_select_time_ms)
     // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
     // place_amb: the per-window tables of ambiguous windows (ipkgpu_db_place_opts)
     DevBuf place_seq, place_off, place_out, place_tables, place_small, place_amb;
@@ -3419,5 +3422,6 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 }  // extern "C"
 
 #include "db_load.hpp"
+#include "db_select.hpp"
 #include "db_place.hpp"
 #include "comm_rccl.hpp"

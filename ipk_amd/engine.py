@@ -434,6 +434,14 @@ def _bind_keymajor(L):
     L.ipkgpu_db_header_of.argtypes = [C.c_void_p]
     L.ipkgpu_db_load_time.restype = C.c_double
     L.ipkgpu_db_load_time.argtypes = [C.c_void_p, C.c_int]
+    L.ipkgpu_db_select.restype = C.c_int
+    L.ipkgpu_db_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_load_select.restype = C.c_int
+    L.ipkgpu_db_load_select.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_float, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_select_time_ms.restype = C.c_double
+    L.ipkgpu_db_select_time_ms.argtypes = [C.c_void_p]
+    L.ipkgpu_db_mu_kmers.restype = C.c_uint64
+    L.ipkgpu_db_mu_kmers.argtypes = [C.c_double, C.c_uint64]
     L.ipkgpu_db_diff.restype = C.c_int
     L.ipkgpu_db_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(DiffCounts), C.c_void_p, C.c_uint64, u64p]
     L.ipkgpu_db_diff_time_ms.restype = C.c_double
@@ -463,6 +471,7 @@ ABI_SYMBOLS += [
     "ipkgpu_parts_spill", "ipkgpu_spill_merge", "ipkgpu_mem_stats", "ipkgpu_get_option",
     "ipkgpu_db_filter_random",
     "ipkgpu_db_load", "ipkgpu_db_header_of", "ipkgpu_db_load_time", "ipkgpu_db_diff", "ipkgpu_db_diff_time_ms", "ipkgpu_db_diff_chunk",
+    "ipkgpu_db_select", "ipkgpu_db_load_select", "ipkgpu_db_select_time_ms", "ipkgpu_db_mu_kmers",
 ]
 
 
@@ -526,6 +535,7 @@ class Db:
     """One owner's shard of the phylo-k-mer database: key -> [(branch, score)] in reference order."""
 
     header = None          # Engine.load_db: the head of the file the database was loaded from (dbfile.file_info's dict)
+    omega = None           # Engine.select_db / load_db with omega=: the omega the selection was made at (Engine.place's default threshold)
 
     def __init__(self, lib, handle):
         self._lib, self._h = lib, handle
@@ -886,26 +896,98 @@ Engine.spill_merge = _spill_merge
 Engine.mem_stats = _mem_stats
 
 
-def _load_db(self, path):
+def mu_kmers(mu, n_kmers):
+    """ipkgpu_db_mu_kmers: the number of k-mers the fraction mu of n_kmers stands for, min(n, ceil(mu * n)) in binary64 (no GPU needed).
+    mu outside [0, 1] or NaN is refused here."""
+    mu = float(mu)
+    if not 0.0 <= mu <= 1.0:
+        raise ValueError(f"mu must be in [0, 1], not {mu}")
+    L = load_library()
+    _bind_keymajor(L)
+    return int(L.ipkgpu_db_mu_kmers(mu, int(n_kmers)))
+
+
+def _selection_args(header, n_kmers, keep_kmers, mu, min_log_score, omega):
+    """(M, t) of a selection from one of keep_kmers / mu and one of min_log_score / omega (none of a pair: all k-mers, every entry)."""
+    if keep_kmers is not None and mu is not None:
+        raise ValueError("give keep_kmers or mu, not both")
+    if min_log_score is not None and omega is not None:
+        raise ValueError("give min_log_score or omega, not both")
+    m = (1 << 64) - 1 if keep_kmers is None else int(keep_kmers)
+    if mu is not None:
+        m = mu_kmers(mu, n_kmers)
+    if m < 0:
+        raise ValueError("keep_kmers must not be negative")
+    t = -np.inf if min_log_score is None else float(min_log_score)
+    if omega is not None:
+        if header is None:
+            raise ValueError("omega= needs a database loaded from a file (sigma and k come from its head); give min_log_score")
+        # in binary32, the type the file stores its omega in and ipkgpu_log_threshold takes: the build's own decimal (1.7) is not below 1.70000005
+        if not np.float32(omega) >= np.float32(header["omega"]):
+            raise ValueError(f"omega {omega} is below the file's omega {header['omega']}: entries under the build's threshold are not in the file")
+        sigma = {"DNA": 4, "AA": 20}.get(header["sequence_type"], 0)
+        t = log_threshold(float(omega), sigma, int(header["kmer_size"]))
+    return min(m, (1 << 64) - 1), t
+
+
+def _finish_selection(self, out, omega):
+    from . import dbfile
+    db = self._adopt(Db(self._lib, out))
+    head = self._lib.ipkgpu_db_header_of(out)
+    db.header = dbfile.info_of_handle(head) if head else None
+    db.omega = None if omega is None else float(omega)
+    return db
+
+
+def _select_db(self, db, keep_kmers=None, mu=None, min_log_score=None, omega=None):
+    """ipkgpu_db_select: the first keep_kmers k-mers of `db` in filter order (or its fraction mu: mu_kmers), of those the entries with
+    score > min_log_score (or above log_threshold(omega, sigma, k) of the database's head) -- a new, ordinary Db; `db` is untouched.
+    The definition is in include/ipkgpu.h and is this library's own.  A selection made with omega= remembers it (`.omega`): Engine.place
+    then takes that omega's threshold by default.  `.header` is the source's with the totals replaced (its omega is not changed)."""
+    _bind_keymajor(self._lib)
+    m, t = _selection_args(db.header, db.num_keys, keep_kmers, mu, min_log_score, omega)
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_db_select(self._h, db._h, m, C.c_float(t), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return _finish_selection(self, out, omega if omega is not None else db.omega)
+
+
+def _select_time_ms(self):
+    """Device time of the engine's last selection (ipkgpu_db_select_time_ms)."""
+    _bind_keymajor(self._lib)
+    return float(self._lib.ipkgpu_db_select_time_ms(self._h))
+
+
+def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=None):
     """ipkgpu_db_load: a database file onto the device -- the Db the builds produce, with the file's filter values and record order
     (filter_values(), filter_order()) and `.header`, the dict dbfile.read_db returns for the file's head.
-    dbfile.write_db_device(engine, db, path, **dbfile.header_args(db.header)) gives the file back byte for byte."""
+    dbfile.write_db_device(engine, db, path, **dbfile.header_args(db.header)) gives the file back byte for byte.
+    With mu, omega, keep_kmers or min_log_score: ipkgpu_db_load_select -- select_db(load_db(path), ...) array for array, reading only the
+    prefix of the file that holds the first k-mers asked for (mu counts against the header's total)."""
     from . import dbfile
     _bind_keymajor(self._lib)
     out = C.c_void_p()
-    rc = self._lib.ipkgpu_db_load(self._h, os.fsencode(path), C.byref(out))
+    if mu is None and omega is None and keep_kmers is None and min_log_score is None:
+        rc = self._lib.ipkgpu_db_load(self._h, os.fsencode(path), C.byref(out))
+        if rc != 0:
+            raise self._err(rc)
+        db = self._adopt(Db(self._lib, out))
+        db.header = dbfile.info_of_handle(self._lib.ipkgpu_db_header_of(out))
+        return db
+    head = dbfile.file_info(path)
+    m, t = _selection_args(head, head["total_num_kmers"], keep_kmers, mu, min_log_score, omega)
+    rc = self._lib.ipkgpu_db_load_select(self._h, os.fsencode(path), m, C.c_float(t), C.byref(out))
     if rc != 0:
         raise self._err(rc)
-    db = self._adopt(Db(self._lib, out))
-    db.header = dbfile.info_of_handle(self._lib.ipkgpu_db_header_of(out))
-    return db
+    return _finish_selection(self, out, omega)
 
 
 def _load_times(self):
     """The engine's last load_db: seconds in all / reading the file / in the host's walk / waiting for the device, and milliseconds of
     db_unpack_heads_kernel, db_unpack_entries_kernel and of all device work behind the last copy (ipkgpu_db_load_time)."""
     _bind_keymajor(self._lib)
-    names = ("total_s", "read_s", "walk_s", "device_wait_s", "heads_ms", "entries_ms", "device_ms")
+    names = ("total_s", "read_s", "walk_s", "device_wait_s", "heads_ms", "entries_ms", "device_ms", "body_bytes_read")
     return {k: float(self._lib.ipkgpu_db_load_time(self._h, i)) for i, k in enumerate(names)}
 
 
@@ -931,6 +1013,8 @@ def _diff_time_ms(self):
 
 
 Engine.load_db = _load_db
+Engine.select_db = _select_db
+Engine.select_time_ms = _select_time_ms
 Engine.load_times = _load_times
 Engine.diff_dbs = _diff_dbs
 Engine.diff_time_ms = _diff_time_ms
@@ -1012,7 +1096,7 @@ def _place_packed(self, db, blob, offsets, keep_at_most=7, sigma=None, k=None, l
             raise ValueError("sigma, k and log_eps are needed for a database that was not loaded from a file")
         sigma = {"DNA": 4, "AA": 20}.get(h["sequence_type"], 0) if sigma is None else sigma
         k = h["kmer_size"] if k is None else k
-        log_eps = log_threshold(h["omega"], sigma, k) if log_eps is None else log_eps
+        log_eps = log_threshold(h["omega"] if db.omega is None else db.omega, sigma, k) if log_eps is None else log_eps
     off = np.ascontiguousarray(offsets, dtype=np.uint64)
     if len(off) < 1:
         raise ValueError("offsets needs one element more than there are queries")
