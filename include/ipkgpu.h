@@ -115,7 +115,8 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * point: per-branch result, key-major with and without owners or positions, key-range passes, ipkgpu_score_groups_positions, the
  * pieces of the on-disk build; results of calls without such a window do not change);
  * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "db_load_chunk_bytes" (bytes of each of the two pinned buffers a file passes
- * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
+ * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "db_load_window_bytes" (bytes of the device window of
+ * ipkgpu_db_load_wanted; 0 = the default, 256 MiB); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
  * "place_lds_branches" (0..4096: the branch count up to which ipkgpu_db_place keeps a query's sums in LDS; 0 = 4096; tests lower it to reach
  * the global tables with small inputs); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
@@ -357,7 +358,7 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
  * first drops the cached blocks and, if it still would, fails with IPKGPU_ERR_NOMEM; work sized by free device memory sees at most what
  * the budget leaves.  The context stays usable after such a failure.  Device memory of the caller (the matrices) is not counted. */
 int ipkgpu_mem_stats(ipkgpu_ctx* ctx, uint64_t* held, uint64_t* held_peak, int reset_peak);
-/* Reads back "workspace_bytes", "device_budget_bytes", "db_load_chunk_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
+/* Reads back "workspace_bytes", "device_budget_bytes", "db_load_chunk_bytes", "db_load_window_bytes" or "slice_long_lists" (a caller that sets them for a while restores them),
  * "debug_sliced_windows" (the windows this context has scored in slices so far), "debug_pool_bytes" (the bytes its pair pool holds), or "last_refused_bytes":
  * the bytes held plus the size of the last allocation the device or the budget refused -- what the failed step needed at least.
  * IPKGPU_ERR_INVALID for other names. */
@@ -574,8 +575,8 @@ int ipkgpu_db_file_check(ipkgpu_db_file* f, uint64_t* n_records, uint64_t* n_ent
  * is IPKGPU_ERR_INVALID before the first of them is launched.  Also IPKGPU_ERR_INVALID: a key in two records, more than
  * 2^32 - 1 records, a record of 2^32 entries or more.  Device memory: the image (the body's bytes, freed before the call returns)
  * plus the database plus 44 bytes per k-mer of workspace and the sort's own, all counted by ipkgpu_mem_stats and held to "device_budget_bytes";
- * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded in pieces
- * (ipkgpu_db_load_select below loads a prefix of it). */
+ * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded whole
+ * (ipkgpu_db_load_select below loads a prefix of it, ipkgpu_db_load_wanted the records a batch of queries can look up). */
 int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out);
 /* The head of the file a database was loaded from (owned by the database); NULL for databases that were not loaded. */
 const ipkgpu_db_file* ipkgpu_db_header_of(const ipkgpu_db* d);
@@ -737,6 +738,64 @@ int ipkgpu_db_place_opts(ipkgpu_ctx* ctx, ipkgpu_db* db, uint32_t sigma, uint32_
                          ipkgpu_placements** out);
 const uint8_t* ipkgpu_placements_strand(const ipkgpu_placements* p);        /* [num_queries] 0 = given, 1 = reverse complement */
 const uint32_t* ipkgpu_placements_n_ambiguous(const ipkgpu_placements* p);  /* [num_queries] expanded (ambiguous) windows */
+
+/* ---- placing on a database file that does not fit device memory: the queries' k-mer set, the restriction, the streamed load --------
+ * Placement never reads a key that none of the queries' windows encodes.  So the database restricted to the codes the queries can
+ * look up gives THE SAME PLACEMENTS BIT FOR BIT -- not a prefix of the file and not a re-ordered sum: every S[b] receives the same
+ * scores in the same window order -- and a batch of 10^5 reads of 150 symbols names at most 1.5 * 10^7 codes whatever the file's size.
+ *
+ * The k-mer set K of (sigma, k, opts, queries): every code ipkgpu_db_place_opts with the same sigma, k and opts would pass to its lookup
+ * for any of the queries -- the codes of the exact windows; with ambiguity = 1 every resolution of every ambiguous window; with
+ * strands = 1 the same for rc(q).  Bytes, windows, letter case, U = T and the ambiguous symbols are those of the placement definition
+ * above.  K is a bitmap on the device of 2^(bits per symbol * k) bits, bit `code` of 32-bit word code >> 5 (at least two words): 512 MiB
+ * at DNA k = 16, 128 MiB at amino acids k = 6.  It counts against "device_budget_bytes" and shows in ipkgpu_mem_stats until it is freed.
+ * One wavefront per query sets the bits with vector atomicOr (kernels_kmerset.hpp); the queries go up in the placement's batches
+ * ("place_batch_queries").  Refusals are ipkgpu_db_place_opts': sigma / k, options, strands = 1 with sigma = 20, a decreasing
+ * seq_off, a query of 2^32 bytes or more; IPKGPU_ERR_NOMEM leaves the context usable. */
+typedef struct ipkgpu_kmer_set ipkgpu_kmer_set;
+int ipkgpu_kmer_set_of_queries(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, const char* seqs, const uint64_t* seq_off, uint64_t n_queries,
+                               const ipkgpu_place_options* opts, ipkgpu_kmer_set** out);
+uint64_t ipkgpu_kmer_set_count(const ipkgpu_kmer_set* set);          /* distinct codes */
+uint64_t ipkgpu_kmer_set_num_words(const ipkgpu_kmer_set* set);      /* 32-bit words of the bitmap: max(2, 2^bits / 32) */
+const uint32_t* ipkgpu_kmer_set_words(ipkgpu_kmer_set* set);         /* host copy of the bitmap, made on first use */
+uint32_t ipkgpu_kmer_set_sigma(const ipkgpu_kmer_set* set);
+uint32_t ipkgpu_kmer_set_k(const ipkgpu_kmer_set* set);
+void ipkgpu_kmer_set_free(ipkgpu_kmer_set* set);
+
+/* The restriction R(D, K) of a database to a k-mer set: the keys of D that are in K, each with ALL its entries in D's order (no score is
+ * compared; a key in K stays even if D gives it no entry), positions if D has them.  Arrays by rule 4 of ipkgpu_db_select, the head by
+ * rule 5.  A key at or beyond 2^bits is in no set: the bound is tested before the bitmap is read.  IPKGPU_ERR_INVALID: a D without
+ * filter arrays (as ipkgpu_db_select), a set or D of another context, a set whose sigma / k are not those of the head of D's file.
+ * Device work and memory: ipkgpu_db_select's, the candidate flags coming from the bitmap instead of the order. */
+int ipkgpu_db_select_keys(ipkgpu_ctx* ctx, const ipkgpu_db* src, const ipkgpu_kmer_set* set, ipkgpu_db** out);
+
+/* ipkgpu_db_select_keys(ipkgpu_db_load_select(path, keep_kmers, min_log_score), set) in every array (keys, offsets, entries,
+ * positions, both filter value arrays, order) and in the head -- WITHOUT an image of the body, and without the database of the file:
+ * the body goes through the two pinned buffers ("db_load_chunk_bytes"), the host walking every chunk, into a device window of
+ * "db_load_window_bytes" (0 = 256 MiB, or the body if that is smaller), and only the wanted records stay (db_stream.hpp,
+ * kernels_dbstream.hpp).  A window holds whole records: it is cut at a record start of the walk; one record longer than the window
+ * grows the window to hold it, or the call returns IPKGPU_ERR_NOMEM.  Per window: db_unpack_heads_kernel, the wanted flags (the
+ * bounded bitmap test: the key is the file's), two scans, the wanted heads and -- through db_unpack_entries_kernel -- the wanted
+ * entries appended in file order.  Behind the last window: the sort of (key, kept record) with the duplicate-key check, the arrays in
+ * key order, the entries moved from file order into key order by entry ranges; then ipkgpu_db_select at min_log_score over the kept
+ * records.  keep_kmers stops the walk after that many records, as ipkgpu_db_load_select does, and reads no chunk behind them; with
+ * keep_kmers at or beyond the header's total the walk must end at the end of the file with the header's totals, as in ipkgpu_db_load.
+ * A file the walk refuses -- in whichever window -- is IPKGPU_ERR_INVALID; what was kept is freed and the context stays usable.
+ * (Unlike the loads above, windows before the damage have been through the kernels by then: every one of their records was walked.)
+ * Device memory at its peak, with W = the window's bytes, n_w = the most records of one window, and kept k-mers n_R and entries e_R
+ * BEFORE min_log_score is applied (e = 8 bytes an entry, 12 with positions):
+ *     bitmap (the caller's)  +  W + 32  +  60 n_w + 24 (the window's workspaces)  +  2 * (24 n_R + e e_R) (the kept arrays, in file
+ *     order; they double when full, so up to twice their content)  +  the scans' own
+ * and behind the last window, the window and its workspaces still held:
+ *     kept arrays  +  R itself (28 n_R + 8 + e e_R, each array rounded up to 256 bytes)  +  20 n_R and the sort's own;
+ * then R and the selection V with ipkgpu_db_select's workspaces.  Every temporary is given back before the call returns.
+ * ipkgpu_db_load_time: as for the other loads, 6 = the host's time in the windows' device work and behind the last window (ms; each
+ * window is waited for), 7 = body bytes read, and 8 = the number of windows, 9 = the records kept before min_log_score.
+ * The duplicate-key check sees only the kept records, and so does the first placement's duplicate-branch check: damage of those
+ * kinds in records the set does not name is NOT seen.  IPKGPU_ERR_INVALID as well: a set of another context, or whose sigma / k are
+ * not the file's. */
+int ipkgpu_db_load_wanted(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set, uint64_t keep_kmers, float min_log_score,
+                          ipkgpu_db** out);
 
 #ifdef __cplusplus
 }

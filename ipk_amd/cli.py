@@ -461,18 +461,31 @@ def _check_selection(db_path, mu, omega):
 @click.option("-o", "--output", required=True, help="the selection's database file")
 @click.option("--mu", type=float, default=None, help="keep the first fraction MU of the file's k-mers in filter order [all]")
 @click.option("--omega", type=float, default=None, help="keep the entries above this omega's threshold; becomes the output's omega [the file's]")
+@click.option("--queries", default=None, type=click.Path(exists=True, dir_okay=False),
+              help="keep only the k-mers these query sequences (FASTA) can look up: the restriction that places them as the whole file does")
+@click.option("--expand-ambiguous", is_flag=True, default=False, help="with --queries: the k-mers `place --expand-ambiguous` looks up")
+@click.option("--strands", type=click.Choice(["given", "both"]), default="given", show_default=True, help="with --queries: the k-mers of both strands")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def subset(db_path, output, mu, omega, device):
+def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, device):
     """Writes a selection of a database file as a database file: the first fraction --mu of its k-mers in filter order, of those
     the entries above --omega's threshold (ipkgpu_db_load_select; the definition is in include/ipkgpu.h and is this engine's own --
     the reference's load(file, mu, omega) could not be read).  The file is loaded as far as the selection needs, selected on the GPU
-    and written by the device writer; the head is the input's with the new totals and, if given, the new omega."""
+    and written by the device writer; the head is the input's with the new totals and, if given, the new omega.
+
+    --queries restricts the selection to the k-mers the reads of a FASTA file can look up (ipkgpu_db_load_wanted: the file is streamed
+    through the GPU in windows and never held whole): `place` of those reads on the output gives what it gives on the input."""
     import ipk_amd
     from ipk_amd import dbfile
     _check_selection(db_path, mu, omega)
     eng = ipk_amd.Engine(device)
     try:
-        d = eng.load_db(db_path, mu=1.0 if mu is None else mu, omega=omega)
+        wanted = None
+        if queries is not None:
+            info = dbfile.file_info(db_path)
+            with open(queries) as fh:
+                seqs = [s for _, s in read_fasta(fh.read())]
+            wanted = eng.kmer_set(seqs, {"DNA": 4, "AA": 20}.get(info["sequence_type"], 0), info["kmer_size"], ambiguity=expand_ambiguous, strands=strands)
+        d = eng.load_db(db_path, mu=1.0 if mu is None else mu, omega=omega, wanted=wanted)
         head = dbfile.header_args(d.header)
         if omega is not None:
             head["omega"] = omega
@@ -495,8 +508,11 @@ def subset(db_path, output, mu, omega, device):
               help="both: place the reverse complement too (DNA) and keep the better strand; adds a seventh column, + or -")
 @click.option("--mu", type=float, default=None, help="place on the first fraction MU of the file's k-mers in filter order only [all]")
 @click.option("--omega", type=float, default=None, help="place at this omega: entries at or below its threshold are left out [the file's]")
+@click.option("--stream-db", is_flag=True, default=False,
+              help="never hold the file on the GPU: stream it in windows and keep only the k-mers the queries look up (same output)")
+@click.option("--query-batch", type=click.IntRange(1), default=None, help="with --stream-db: queries per pass over the file [all]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, device):
+def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, stream_db, query_batch, device):
     """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
     branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
 
@@ -506,22 +522,31 @@ def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous,
     alphabet (N, X, ...) end a k-mer; --expand-ambiguous and --strands both change that (ipkgpu_db_place_opts in include/ipkgpu.h).
 
     --mu / --omega load a selection of the file (ipkgpu_db_load_select: only the prefix of the file that holds the first k-mers is
-    read) and place on it, at --omega's threshold; what `subset` with the same options writes places alike."""
+    read) and place on it, at --omega's threshold; what `subset` with the same options writes places alike.
+
+    --stream-db is for a file that does not fit the GPU's memory: per --query-batch queries the file goes through the GPU in bounded
+    windows and only the k-mers those queries can look up stay (ipkgpu_db_load_wanted).  The TSV is the same."""
     import ipk_amd
     _check_selection(db_path, mu, omega)
     with open(queries) as fh:
         recs = read_fasta(fh.read())
     eng = ipk_amd.Engine(device)
     try:
-        d = eng.load_db(db_path, mu=mu, omega=omega)
-        res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
+        d = None
+        if stream_db:
+            res = eng.place_file(db_path, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands, mu=mu, omega=omega,
+                                 query_batch=query_batch)
+        else:
+            d = eng.load_db(db_path, mu=mu, omega=omega)
+            res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
         text = "".join(line + "\n" for line in placement_lines([n for n, _ in recs], res, keep_factor, strands == "both"))
         if output:
             with open(output, "w") as fh:
                 fh.write(text)
         else:
             click.echo(text, nl=False)
-        d.free()
+        if d is not None:
+            d.free()
     finally:
         eng.close()
 

@@ -12,7 +12,7 @@
 extern "C" {
 
 const ipkgpu_db_file* ipkgpu_db_header_of(const ipkgpu_db* d) { return d ? d->file : nullptr; }
-double ipkgpu_db_load_time(const ipkgpu_ctx* ctx, int which) { return ctx && which >= 0 && which < 8 ? ctx->t_load[which] : 0; }
+double ipkgpu_db_load_time(const ipkgpu_ctx* ctx, int which) { return ctx && which >= 0 && which < 10 ? ctx->t_load[which] : 0; }
 double ipkgpu_db_diff_time_ms(const ipkgpu_ctx* ctx) { return ctx ? ctx->t_diff_ms : 0; }
 uint32_t ipkgpu_db_diff_chunk(void) { return DB_DIFF_CHUNK; }
 
@@ -178,7 +178,7 @@ int db_load_records(ipkgpu_ctx* ctx, const char* path, uint64_t keep_records, ip
         HIP_TRY(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_sk, d_sorted, (size_t)n, 0, 64, ctx->stream));
         RC_TRY(ensure(ctx, ctx->tmp_c, tmp_bytes));
         HIP_TRY(ctx, rocprim::radix_sort_keys(ctx->tmp_c.p, tmp_bytes, d_sk, d_sorted, (size_t)n, 0, 64, ctx->stream));
-        hipLaunchKernelGGL(db_load_order_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_sorted, d_starts, d_fvb, d_cnt, n, db->d_keys, d_cnt_sorted,
+        hipLaunchKernelGGL(db_load_order_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, d_sorted, d_starts, d_fvb, d_cnt, n, db->d_keys, d_cnt_sorted,
                            d_body_off, db->d_fv32, db->d_fv64, db->d_order, d_dup);
         HIP_TRY(ctx, hipGetLastError());
         RC_TRY(scan_u32(ctx, d_cnt_sorted, n, db->d_key_off));
@@ -211,6 +211,7 @@ int db_load_records(ipkgpu_ctx* ctx, const char* path, uint64_t keep_records, ip
     ctx->t_load[1] = t_read; ctx->t_load[2] = t_walk; ctx->t_load[3] = t_wait;
     ctx->t_load[4] = n ? sw.ms(eh, e1) : 0; ctx->t_load[5] = n ? sw.ms(e2, e3) : 0; ctx->t_load[6] = db->t_merge;
     ctx->t_load[7] = (double)bytes_read;
+    ctx->t_load[8] = 0; ctx->t_load[9] = 0;                              // (windows and records kept: ipkgpu_db_load_wanted's)
     db->file = file; fguard.f = nullptr;
     guard.r = nullptr;
     *out = db;

@@ -24,7 +24,19 @@ ipkgpu_db_file* select_head(const ipkgpu_db_file* src, uint64_t n, uint64_t ne)
     return f;
 }
 
-int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float t, ipkgpu_db** out)
+// Is `set` a k-mer set of this context over the codes of the file head `file` (NULL: nothing to compare with)?
+int set_fits(ipkgpu_ctx* ctx, const ipkgpu_kmer_set* set, const ipkgpu_db_file* file)
+{
+    if (!set || set->ctx != ctx) return fail(ctx, IPKGPU_ERR_INVALID, "a k-mer set of this context is needed");
+    if (file && (file->head.sequence_type != (set->sigma == 4 ? "DNA" : "AA") || file->head.kmer_size != set->k))
+        return fail(ctx, IPKGPU_ERR_INVALID, "the k-mer set is of sigma %u and k = %u, the database's file of %s and k = %llu", set->sigma, set->k,
+                    file->head.sequence_type.c_str(), (unsigned long long)file->head.kmer_size);
+    return IPKGPU_OK;
+}
+
+// set == NULL: the selection at (keep_kmers, t).  With a set (ipkgpu_db_select_keys; keep_kmers and t are not looked at): the
+// candidates are the keys in the set, a candidate keeps every entry and stays even without one -- the same scans and copies.
+int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float t, ipkgpu_db** out, const ipkgpu_kmer_set* set = nullptr)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (out) *out = nullptr;
@@ -32,7 +44,8 @@ int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float 
     if (t != t) return fail(ctx, IPKGPU_ERR_INVALID, "min_log_score is NaN");
     if (!src->d_fv32 || !src->d_fv64 || !src->d_order)
         return fail(ctx, IPKGPU_ERR_INVALID, "the database has no filter values and order (filter it, or load it from a file): nothing to select by");
-    const uint64_t n = src->n_keys, ne = src->n_entries, m = std::min(keep_kmers, n);
+    if (set) RC_TRY(set_fits(ctx, set, src->file));
+    const uint64_t n = src->n_keys, ne = src->n_entries, m = set ? n : std::min(keep_kmers, n);
     const bool positioned = src->d_positions != nullptr;
     if ((ne + DB_UNPACK_TILE - 1) / DB_UNPACK_TILE > 0x7FFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "too many entries for one launch");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -48,7 +61,7 @@ int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float 
     const uint32_t tiles = (uint32_t)((ne + DB_UNPACK_TILE - 1) / DB_UNPACK_TILE);
     uint32_t *d_cand = nullptr, *d_keep = nullptr, *d_key_keep = nullptr, *d_rec_keep = nullptr;
     uint64_t *d_e_scan = nullptr, *d_k_scan = nullptr, *d_r_scan = nullptr;
-    if (m && ne) {                                            // (no candidate or no entry at all: the empty selection, nothing launched)
+    if (set ? n != 0 : (m && ne)) {                           // (no candidate or no entry at all: the empty selection, nothing launched)
         // workspaces: per entry the keep flag and its scan; per key the candidate flag, the key's flag and its scan; per record i < M the same
         RC_TRY(ensure(ctx, ctx->tmp_a, ne * 4));
         RC_TRY(ensure(ctx, ctx->tmp_b, (ne + 1) * 8));
@@ -60,7 +73,11 @@ int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float 
         d_keep = ctx->tmp_a.as<uint32_t>(); d_e_scan = ctx->tmp_b.as<uint64_t>();
         d_cand = ctx->counts.as<uint32_t>(); d_key_keep = ctx->sp_pops.as<uint32_t>(); d_k_scan = ctx->goff.as<uint64_t>();
         d_rec_keep = ctx->sp_c16.as<uint32_t>(); d_r_scan = ctx->sp_rank.as<uint64_t>();
-        if (m < n) {
+        if (set) {
+            hipLaunchKernelGGL(db_select_wanted_kernel, dim3(kb), dim3(256), 0, ctx->stream, src->d_keys, n, set->d_words, set->n_codes, d_cand);
+            if (ne) hipLaunchKernelGGL((db_select_flag_kernel<false, false>), dim3(tiles), dim3(256), 0, ctx->stream, src->d_entries, src->d_key_off, d_cand, n, ne, t, d_keep);
+            d_key_keep = d_cand;                              // (a wanted key stays, with or without entries)
+        } else if (m < n) {
             HIP_TRY(ctx, hipMemsetAsync(d_cand, 0, n * 4, ctx->stream));
             hipLaunchKernelGGL(db_select_mark_kernel, dim3(mb), dim3(256), 0, ctx->stream, src->d_order, m, d_cand);
             hipLaunchKernelGGL(db_select_flag_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, src->d_entries, src->d_key_off, d_cand, n, ne, t, d_keep);
@@ -69,7 +86,7 @@ int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float 
         }
         HIP_TRY(ctx, hipGetLastError());
         RC_TRY(scan_u32(ctx, d_keep, ne, d_e_scan));
-        hipLaunchKernelGGL(db_select_keys_kernel, dim3(kb), dim3(256), 0, ctx->stream, src->d_key_off, d_e_scan, n, d_key_keep);
+        if (!set) hipLaunchKernelGGL(db_select_keys_kernel, dim3(kb), dim3(256), 0, ctx->stream, src->d_key_off, d_e_scan, n, d_key_keep);
         HIP_TRY(ctx, hipGetLastError());
         RC_TRY(scan_u32(ctx, d_key_keep, n, d_k_scan));
         hipLaunchKernelGGL(db_select_records_kernel, dim3(mb), dim3(256), 0, ctx->stream, src->d_order, d_key_keep, m, d_rec_keep);
@@ -88,7 +105,8 @@ int db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float 
     if (n_out == 0) {                                         // (a kept key has a kept entry: no key, no entry)
         HIP_TRY(ctx, hipMemsetAsync(db->d_key_off, 0, 8, ctx->stream));
     } else {
-        if (positioned) hipLaunchKernelGGL(db_select_copy_kernel<true>, dim3(tiles), dim3(256), 0, ctx->stream, src->d_entries, src->d_positions, d_keep, d_e_scan, ne,
+        if (!ne) {}
+        else if (positioned) hipLaunchKernelGGL(db_select_copy_kernel<true>, dim3(tiles), dim3(256), 0, ctx->stream, src->d_entries, src->d_positions, d_keep, d_e_scan, ne,
                                            db->d_entries, db->d_positions);
         else hipLaunchKernelGGL(db_select_copy_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, src->d_entries, (const uint32_t*)nullptr, d_keep, d_e_scan, ne,
                                 db->d_entries, (uint32_t*)nullptr);
@@ -126,6 +144,14 @@ double ipkgpu_db_select_time_ms(const ipkgpu_ctx* ctx) { return ctx ? ctx->t_sel
 int ipkgpu_db_select(ipkgpu_ctx* ctx, const ipkgpu_db* src, uint64_t keep_kmers, float min_log_score, ipkgpu_db** out)
 {
     return db_select(ctx, src, keep_kmers, min_log_score, out);
+}
+
+int ipkgpu_db_select_keys(ipkgpu_ctx* ctx, const ipkgpu_db* src, const ipkgpu_kmer_set* set, ipkgpu_db** out)
+{
+    if (!ctx) return IPKGPU_ERR_INVALID;
+    if (out) *out = nullptr;
+    if (!set) return fail(ctx, IPKGPU_ERR_INVALID, "a k-mer set of this context is needed");
+    return db_select(ctx, src, ~(uint64_t)0, 0.0f, out, set);
 }
 
 int ipkgpu_db_load_select(ipkgpu_ctx* ctx, const char* path, uint64_t keep_kmers, float min_log_score, ipkgpu_db** out)

@@ -45,6 +45,8 @@
 #include "kernels_dbselect.hpp"
 #include "kernels_dbdiff.hpp"
 #include "kernels_place.hpp"
+#include "kernels_kmerset.hpp"
+#include "kernels_dbstream.hpp"
 #include "db_file.hpp"
 #include "spill_format.hpp"
 #include <sys/mman.h>
@@ -176,7 +178,8 @@ struct ipkgpu_ctx {
     uint64_t last_entries = 0; uint32_t last_gb = 0;   // the key-major writer's output of the previous batch: the next one's estimate
     double t_write_total = 0, t_write_device = 0, t_write_file = 0;   // last ipkgpu_db_write
     int64_t opt_load_chunk = 0;          // "db_load_chunk_bytes": bytes per pinned buffer of ipkgpu_db_load (0: SPILL_STAGE, the spill blocks')
-    double t_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load / ipkgpu_db_load_select (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
+    int64_t opt_load_window = 0;         // "db_load_window_bytes": bytes of the device window of ipkgpu_db_load_wanted (0: DB_STREAM_WINDOW)
+    double t_load[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load / _load_select / _load_wanted (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
     double t_diff_ms = 0;
     double t_select_ms = 0;              // device time of the last ipkgpu_db_select (ipkgpu_db_select_time_ms)
     // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
@@ -252,6 +255,17 @@ struct ipkgpu_db {
     uint32_t* d_place_index = nullptr;
     uint32_t place_bits = 0, place_shift = 0, place_slots = 0, place_branches = 0;
     double t_place_index = 0;
+};
+
+// ipkgpu_kmer_set_of_queries (db_kmerset.hpp): the bitmap over the 2^bits codes of (sigma, k), taken through dev_malloc
+struct ipkgpu_kmer_set {
+    ipkgpu_ctx* ctx = nullptr;
+    uint32_t sigma = 0, k = 0, bits = 0;
+    uint64_t n_codes = 0, n_words = 0, count = 0;
+    uint32_t* d_words = nullptr;
+    size_t bytes = 0;
+    std::vector<uint32_t> h_words;
+    bool h_ok = false;
 };
 
 static std::string g_create_err;
@@ -535,6 +549,11 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
     if (!strcmp(name, "db_load_chunk_bytes")) {
         if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "db_load_chunk_bytes must not be negative (0 = the default)");
         ctx->opt_load_chunk = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "db_load_window_bytes")) {
+        if (value < 0) return fail(ctx, IPKGPU_ERR_INVALID, "db_load_window_bytes must not be negative (0 = the default)");
+        ctx->opt_load_window = value;
         return IPKGPU_OK;
     }
     if (!strcmp(name, "place_batch_queries")) {
@@ -3199,6 +3218,7 @@ int ipkgpu_get_option(const ipkgpu_ctx* ctx, const char* name, int64_t* value)
     if (!strcmp(name, "last_refused_bytes")) { *value = (int64_t)ctx->refused_need; return IPKGPU_OK; }
     if (!strcmp(name, "slice_long_lists")) { *value = ctx->opt_slice; return IPKGPU_OK; }
     if (!strcmp(name, "db_load_chunk_bytes")) { *value = ctx->opt_load_chunk; return IPKGPU_OK; }
+    if (!strcmp(name, "db_load_window_bytes")) { *value = ctx->opt_load_window; return IPKGPU_OK; }
     if (!strcmp(name, "place_batch_queries")) { *value = ctx->opt_place_batch; return IPKGPU_OK; }
     if (!strcmp(name, "place_lds_branches")) { *value = ctx->opt_place_lds; return IPKGPU_OK; }
     if (!strcmp(name, "debug_sliced_windows")) { *value = (int64_t)ctx->sliced_windows; return IPKGPU_OK; }
@@ -3424,4 +3444,6 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 #include "db_load.hpp"
 #include "db_select.hpp"
 #include "db_place.hpp"
+#include "db_kmerset.hpp"
+#include "db_stream.hpp"
 #include "comm_rccl.hpp"

@@ -41,6 +41,9 @@ __global__ __launch_bounds__(256) void db_unpack_heads_kernel(const unsigned cha
 }
 
 // One thread per key position j of the sorted (key, record) list.  order[record] = j: keys[order[i]] is the file's i-th record.
+// BODY: starts are record starts in the image and body_off the places of the records' entries there; false (the streamed load,
+// kernels_dbstream.hpp): starts are already the places of the records' entries, in its file-order entry array, and go through as they are.
+template <bool BODY = true>
 __global__ __launch_bounds__(256) void db_load_order_kernel(const unsigned long long* __restrict__ sorted, const uint64_t* __restrict__ starts,
                                                             const uint32_t* __restrict__ fv_bits, const uint32_t* __restrict__ counts, uint64_t n,
                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ counts_sorted,
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(256) void db_load_order_kernel(const unsigned long 
     if (j > 0 && (uint32_t)(sorted[j - 1] >> 32) == key) atomicOr(duplicate, 1u);
     keys[j] = key;
     counts_sorted[j] = counts[rec];
-    body_off[j] = starts[rec] + ipkfmt::RECORD_HEAD_BYTES;
+    body_off[j] = starts[rec] + (BODY ? ipkfmt::RECORD_HEAD_BYTES : 0);
     const float f = __uint_as_float(fv_bits[rec]);
     fv32[j] = f;
     fv64[j] = (double)f;

@@ -2,6 +2,7 @@
 // (ipkgpu_db_select in include/ipkgpu.h; the definition is this library's own -- i2l::load(file, mu, omega) is un-vendored).
 //
 //   db_select_mark_kernel      candidate flags scattered from order[0 .. M)
+//   db_select_wanted_kernel    candidate flags of ipkgpu_db_select_keys: is the key's bit set in a k-mer set's bitmap (db_key_wanted)
 //   db_select_flag_kernel      per ENTRY: keep = its key is a candidate and score > t          (entry ranges, as db_unpack_entries_kernel)
 //   db_select_keys_kernel      per key: does an entry of it stay (two reads of the scanned keep flags)
 //   db_select_records_kernel   per record i < M: does its key stay
@@ -21,11 +22,26 @@ __global__ __launch_bounds__(256) void db_select_mark_kernel(const uint32_t* __r
     if (i < m) cand[order[i]] = 1u;
 }
 
+// Is `key` in the k-mer set whose bitmap holds n_codes bits?  The bound is tested before the bitmap is read: a key can come from a file,
+// which no host check covers, and a key at or beyond n_codes is in no set.
+__device__ __forceinline__ bool db_key_wanted(const uint32_t* __restrict__ bitmap, uint64_t n_codes, uint32_t key)
+{
+    if ((uint64_t)key >= n_codes) return false;
+    return ((bitmap[key >> 5] >> (key & 31u)) & 1u) != 0u;
+}
+
+__global__ __launch_bounds__(256) void db_select_wanted_kernel(const uint32_t* __restrict__ keys, uint64_t n_keys, const uint32_t* __restrict__ bitmap,
+                                                               uint64_t n_codes, uint32_t* __restrict__ cand)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < n_keys) cand[j] = db_key_wanted(bitmap, n_codes, keys[j]) ? 1u : 0u;
+}
+
 // Work by ENTRY ranges (DB_UNPACK_TILE entries per workgroup, whatever keys they belong to).  ALL: every key is a candidate, no key is
-// looked up.  Otherwise the keys a tile touches are found once and each lane finds its entry's key among those (db_key_of_entry: the
+// looked up.  SCORE false (ipkgpu_db_select_keys): no score is compared, a candidate keeps every entry whatever its bits.  Otherwise the keys a tile touches are found once and each lane finds its entry's key among those (db_key_of_entry: the
 // last key whose offset is not beyond the entry, so keys without entries are passed over).  The comparison is binary32 and strict; a
 // NaN score fails it.
-template <bool ALL>
+template <bool ALL, bool SCORE = true>
 __global__ __launch_bounds__(256) void db_select_flag_kernel(const uint2* __restrict__ entries, const uint64_t* __restrict__ key_off,
                                                              const uint32_t* __restrict__ cand, uint64_t n_keys, uint64_t n_entries, float t,
                                                              uint32_t* __restrict__ keep)
@@ -43,7 +59,7 @@ __global__ __launch_bounds__(256) void db_select_flag_kernel(const uint2* __rest
         const uint64_t e = e0 + r * 256 + threadIdx.x;
         if (e > e_last) break;
         const uint2 ent = entries[e];
-        bool k = __uint_as_float(ent.y) > t;
+        bool k = !SCORE || __uint_as_float(ent.y) > t;
         if (!ALL) k = k && cand[db_key_of_entry(key_off, j_lo, j_hi, e)] != 0u;
         keep[e] = k ? 1u : 0u;
     }

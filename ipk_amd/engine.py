@@ -939,12 +939,14 @@ def _finish_selection(self, out, omega):
     return db
 
 
-def _select_db(self, db, keep_kmers=None, mu=None, min_log_score=None, omega=None):
+def _select_db(self, db, keep_kmers=None, mu=None, min_log_score=None, omega=None, wanted=None):
     """ipkgpu_db_select: the first keep_kmers k-mers of `db` in filter order (or its fraction mu: mu_kmers), of those the entries with
     score > min_log_score (or above log_threshold(omega, sigma, k) of the database's head) -- a new, ordinary Db; `db` is untouched.
     The definition is in include/ipkgpu.h and is this library's own.  A selection made with omega= remembers it (`.omega`): Engine.place
     then takes that omega's threshold by default.  `.header` is the source's with the totals replaced (its omega is not changed)."""
     _bind_keymajor(self._lib)
+    if wanted is not None:
+        return _select_wanted(self, db, keep_kmers, mu, min_log_score, omega, wanted)
     m, t = _selection_args(db.header, db.num_keys, keep_kmers, mu, min_log_score, omega)
     out = C.c_void_p()
     rc = self._lib.ipkgpu_db_select(self._h, db._h, m, C.c_float(t), C.byref(out))
@@ -959,15 +961,25 @@ def _select_time_ms(self):
     return float(self._lib.ipkgpu_db_select_time_ms(self._h))
 
 
-def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=None):
+def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=None, wanted=None):
     """ipkgpu_db_load: a database file onto the device -- the Db the builds produce, with the file's filter values and record order
     (filter_values(), filter_order()) and `.header`, the dict dbfile.read_db returns for the file's head.
     dbfile.write_db_device(engine, db, path, **dbfile.header_args(db.header)) gives the file back byte for byte.
     With mu, omega, keep_kmers or min_log_score: ipkgpu_db_load_select -- select_db(load_db(path), ...) array for array, reading only the
-    prefix of the file that holds the first k-mers asked for (mu counts against the header's total)."""
+    prefix of the file that holds the first k-mers asked for (mu counts against the header's total).
+    With wanted= (a KmerSet of Engine.kmer_set): ipkgpu_db_load_wanted -- select_db(load_db(path, ...), wanted=wanted) array for array, the
+    file streamed through a device window of option "db_load_window_bytes" and never held whole: for a file larger than device memory."""
     from . import dbfile
     _bind_keymajor(self._lib)
     out = C.c_void_p()
+    if wanted is not None:
+        _bind_stream(self._lib)
+        head = dbfile.file_info(path)
+        m, t = _selection_args(head, head["total_num_kmers"], keep_kmers, mu, min_log_score, omega)
+        rc = self._lib.ipkgpu_db_load_wanted(self._h, os.fsencode(path), wanted._h, m, C.c_float(t), C.byref(out))
+        if rc != 0:
+            raise self._err(rc)
+        return _finish_selection(self, out, omega)
     if mu is None and omega is None and keep_kmers is None and min_log_score is None:
         rc = self._lib.ipkgpu_db_load(self._h, os.fsencode(path), C.byref(out))
         if rc != 0:
@@ -985,9 +997,10 @@ def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=Non
 
 def _load_times(self):
     """The engine's last load_db: seconds in all / reading the file / in the host's walk / waiting for the device, and milliseconds of
-    db_unpack_heads_kernel, db_unpack_entries_kernel and of all device work behind the last copy (ipkgpu_db_load_time)."""
+    db_unpack_heads_kernel, db_unpack_entries_kernel and of all device work behind the last copy; the body bytes read; and for a
+    load with wanted= the number of windows and the records kept (ipkgpu_db_load_time)."""
     _bind_keymajor(self._lib)
-    names = ("total_s", "read_s", "walk_s", "device_wait_s", "heads_ms", "entries_ms", "device_ms", "body_bytes_read")
+    names = ("total_s", "read_s", "walk_s", "device_wait_s", "heads_ms", "entries_ms", "device_ms", "body_bytes_read", "windows", "records_kept")
     return {k: float(self._lib.ipkgpu_db_load_time(self._h, i)) for i, k in enumerate(names)}
 
 
@@ -1134,3 +1147,159 @@ def _place(self, db, seqs, keep_at_most=7, sigma=None, k=None, log_eps=None, amb
 
 Engine.place_packed = _place_packed
 Engine.place = _place
+
+
+# ---- placing on a file that does not fit device memory: the queries' k-mer set, the restriction, the streamed load -----------------
+
+ABI_SYMBOLS += [
+    "ipkgpu_kmer_set_of_queries", "ipkgpu_kmer_set_count", "ipkgpu_kmer_set_num_words", "ipkgpu_kmer_set_words", "ipkgpu_kmer_set_sigma",
+    "ipkgpu_kmer_set_k", "ipkgpu_kmer_set_free", "ipkgpu_db_select_keys", "ipkgpu_db_load_wanted",
+]
+
+ERR_NOMEM = 3
+
+
+def _bind_stream(L):
+    if getattr(L, "_stream_bound", False):
+        return
+    _bind_place(L)
+    L.ipkgpu_kmer_set_of_queries.restype = C.c_int
+    L.ipkgpu_kmer_set_of_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(_PlaceOptions),
+                                             C.POINTER(C.c_void_p)]
+    L.ipkgpu_kmer_set_count.restype = C.c_uint64
+    L.ipkgpu_kmer_set_num_words.restype = C.c_uint64
+    L.ipkgpu_kmer_set_words.restype = C.POINTER(C.c_uint32)
+    L.ipkgpu_kmer_set_sigma.restype = C.c_uint32
+    L.ipkgpu_kmer_set_k.restype = C.c_uint32
+    L.ipkgpu_kmer_set_free.restype = None
+    for name in ("count", "num_words", "words", "sigma", "k", "free"):
+        getattr(L, "ipkgpu_kmer_set_" + name).argtypes = [C.c_void_p]
+    L.ipkgpu_db_select_keys.restype = C.c_int
+    L.ipkgpu_db_select_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_load_wanted.restype = C.c_int
+    L.ipkgpu_db_load_wanted.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_void_p)]
+    L._stream_bound = True
+
+
+class KmerSet:
+    """The k-mer set of a batch of queries (ipkgpu_kmer_set_of_queries): a bitmap over the code space on the device.  count: the distinct
+    codes; words(): a host copy of the bitmap, bit `code` of 32-bit word code >> 5."""
+
+    def __init__(self, lib, handle):
+        self._lib, self._h = lib, handle
+        self.count = int(lib.ipkgpu_kmer_set_count(handle))
+        self.sigma, self.k = int(lib.ipkgpu_kmer_set_sigma(handle)), int(lib.ipkgpu_kmer_set_k(handle))
+
+    def words(self):
+        n = int(self._lib.ipkgpu_kmer_set_num_words(self._h))
+        p = self._lib.ipkgpu_kmer_set_words(self._h)
+        if not p:
+            raise MemoryError("no host copy of the k-mer set")
+        return np.ctypeslib.as_array(p, shape=(n,)).copy()
+
+    def free(self):
+        if self._h:
+            self._lib.ipkgpu_kmer_set_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _pack(seqs):
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    off = np.zeros(len(raw) + 1, np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return np.frombuffer(b"".join(raw), np.uint8), off
+
+
+def _kmer_set(self, seqs, sigma, k, ambiguity=False, strands="given"):
+    """ipkgpu_kmer_set_of_queries: every k-mer code Engine.place(db, seqs, ambiguity=, strands=) would look up -> KmerSet.
+    A database restricted to it (select_db / load_db with wanted=) places `seqs` bit for bit as the whole database does."""
+    if strands not in ("given", "both"):
+        raise ValueError('strands is "given" or "both"')
+    _bind_keymajor(self._lib)
+    _bind_stream(self._lib)
+    data, off = _pack(seqs)
+    opts = _PlaceOptions(int(bool(ambiguity)), int(strands == "both"))
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_kmer_set_of_queries(self._h, int(sigma), int(k), data.ctypes.data, off.ctypes.data, len(off) - 1, C.byref(opts), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return self._adopt(KmerSet(self._lib, out))
+
+
+def _select_wanted(self, db, keep_kmers, mu, min_log_score, omega, wanted):
+    """select_db(db, ..., wanted=set): the selection, if one is asked for, then its restriction to the set (ipkgpu_db_select_keys)."""
+    _bind_stream(self._lib)
+    src = db
+    if not (keep_kmers is None and mu is None and min_log_score is None and omega is None):
+        src = _select_db(self, db, keep_kmers, mu, min_log_score, omega)
+    try:
+        out = C.c_void_p()
+        rc = self._lib.ipkgpu_db_select_keys(self._h, src._h, wanted._h, C.byref(out))
+        if rc != 0:
+            raise self._err(rc)
+        return _finish_selection(self, out, src.omega)
+    finally:
+        if src is not db:
+            src.free()
+
+
+def _place_file(self, path, seqs, keep_at_most=7, ambiguity=False, strands="given", mu=None, omega=None, query_batch=None):
+    """Places `seqs` on the database FILE `path` without ever holding the file on the device: for each batch of query_batch queries
+    (None: all at once) the batch's k-mer set, the streamed load of the records it names (load_db(path, mu=, omega=, wanted=set)), the
+    placement, and both freed -> one Placements over all queries, equal to place(load_db(path, mu=, omega=), seqs, ...).
+    A batch whose restricted database does not fit (IPKGPU_ERR_NOMEM) is retried in halves, down to one query; then the error stands."""
+    from . import dbfile
+    seqs = list(seqs)
+    head = dbfile.file_info(path)
+    sigma = {"DNA": 4, "AA": 20}.get(head["sequence_type"], 0)
+    k = int(head["kmer_size"])
+    step = len(seqs) if query_batch is None else int(query_batch)
+    if query_batch is not None and step < 1:
+        raise ValueError("query_batch must be at least 1")
+    parts = []
+
+    def run(batch):
+        try:
+            kset = self.kmer_set(batch, sigma, k, ambiguity, strands)
+            try:
+                db = self.load_db(path, mu=mu, omega=omega, wanted=kset)
+                try:
+                    parts.append(self.place(db, batch, keep_at_most, ambiguity=ambiguity, strands=strands))
+                finally:
+                    db.free()
+            finally:
+                kset.free()
+        except IpkGpuError as e:
+            if e.code != ERR_NOMEM or len(batch) < 2:
+                raise
+            half = (len(batch) + 1) // 2
+            run(batch[:half])
+            run(batch[half:])
+
+    for i in range(0, len(seqs), max(step, 1)):
+        run(seqs[i:i + step])
+    if not parts:
+        run([])
+    return _concat_placements(parts)
+
+
+def _concat_placements(parts):
+    if len(parts) == 1:
+        return parts[0]
+    res = object.__new__(Placements)
+    res.n, res.keep = sum(p.n for p in parts), parts[0].keep
+    for name in ("branches", "scores", "counts", "lwr", "n_kmers", "n_found", "n_branches", "strand", "n_ambiguous"):
+        setattr(res, name, np.concatenate([getattr(p, name) for p in parts]))
+    res.time_ms = {key: sum(p.time_ms[key] for p in parts) for key in parts[0].time_ms}
+    return res
+
+
+Engine.kmer_set = _kmer_set
+Engine.place_file = _place_file
