@@ -116,7 +116,7 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * pieces of the on-disk build; results of calls without such a window do not change);
  * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "db_load_chunk_bytes" (bytes of each of the two pinned buffers a file passes
  * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "db_load_window_bytes" (bytes of the device window of
- * ipkgpu_db_load_wanted; 0 = the default, 256 MiB); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
+ * ipkgpu_db_load_wanted and ipkgpu_db_load_key_range; 0 = the default, 256 MiB -- in ipkgpu_db_diff_files a sixteenth of what the budget leaves); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
  * "place_lds_branches" (0..4096: the branch count up to which ipkgpu_db_place keeps a query's sums in LDS; 0 = 4096; tests lower it to reach
  * the global tables with small inputs); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
@@ -576,7 +576,8 @@ int ipkgpu_db_file_check(ipkgpu_db_file* f, uint64_t* n_records, uint64_t* n_ent
  * 2^32 - 1 records, a record of 2^32 entries or more.  Device memory: the image (the body's bytes, freed before the call returns)
  * plus the database plus 44 bytes per k-mer of workspace and the sort's own, all counted by ipkgpu_mem_stats and held to "device_budget_bytes";
  * what does not fit is IPKGPU_ERR_NOMEM and leaves the context usable.  A file larger than device memory is not loaded whole
- * (ipkgpu_db_load_select below loads a prefix of it, ipkgpu_db_load_wanted the records a batch of queries can look up). */
+ * (ipkgpu_db_load_select below loads a prefix of it, ipkgpu_db_load_wanted the records a batch of queries can look up,
+ * ipkgpu_db_load_key_range the records of a key range, and ipkgpu_db_diff_files compares two such files range by range). */
 int ipkgpu_db_load(ipkgpu_ctx* ctx, const char* path, ipkgpu_db** out);
 /* The head of the file a database was loaded from (owned by the database); NULL for databases that were not loaded. */
 const ipkgpu_db_file* ipkgpu_db_header_of(const ipkgpu_db* d);
@@ -796,6 +797,80 @@ int ipkgpu_db_select_keys(ipkgpu_ctx* ctx, const ipkgpu_db* src, const ipkgpu_km
  * not the file's. */
 int ipkgpu_db_load_wanted(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set, uint64_t keep_kmers, float min_log_score,
                           ipkgpu_db** out);
+
+/* ---- comparing database files that do not fit device memory, by key ranges ------------------------------------------------------------
+ * The records of a file whose key lies in [key_lo, key_hi), key_lo <= key_hi <= 2^32 (else IPKGPU_ERR_INVALID): every kept key with
+ * all its entries, a record without entries included -- the call makes no selection and drops no key.  Arrays and head by the rules of
+ * ipkgpu_db_select_keys (keys ascending, filter values bit for bit, the order renumbered, the head's totals replaced).  It is the
+ * streamed load of ipkgpu_db_load_wanted with a second predicate (db_stream_flag_range_kernel in place of the bitmap test): the same
+ * windows, the same walk of the WHOLE file with its end-of-file and totals checks on every call, the same duplicate-key check over the
+ * kept records, the same memory (no bitmap).  key_lo == key_hi: an empty database and IPKGPU_OK, the file walked and checked all
+ * the same. */
+int ipkgpu_db_load_key_range(ipkgpu_ctx* ctx, const char* path, uint64_t key_lo, uint64_t key_hi, ipkgpu_db** out);
+
+/* ipkgpu_db_diff(ipkgpu_db_load(path_a), ipkgpu_db_load(path_b), eps, ...) field for field and bit for bit -- positions_differ, the
+ * bits of max_abs_diff and the order of the records included -- with neither file ever resident whole (db_diff_files.hpp).
+ * A comparison composes exactly over disjoint ascending key ranges: every count adds, max_abs_diff is the maximum, the record list is
+ * the concatenation.  Per range: A's range and B's range through the key-range load, ipkgpu_db_diff, the counts added, the records
+ * appended until max_records is reached OVER ALL ranges (the counts stay exact behind that), both range databases freed.
+ *
+ * The plan.  avail = what "device_budget_bytes" leaves beside what the context holds, without a budget the device's free memory; the
+ * context's cached result blocks and the workspaces ipkgpu_db_diff and the scans cache are given back first, after every range and
+ * when the call returns.  If range_bytes (below) at the two heads' totals is at most avail there is ONE range [0, 2^32) and each file
+ * is read once.  Otherwise one HISTOGRAM PASS over each file: streamed as a load that keeps nothing, per window
+ * db_unpack_heads_kernel and db_stream_hist_kernel (kernels_dbstream.hpp), which adds 1 to rec_hist[bin] (u32) and the record's
+ * entry count to ent_hist[bin] (u64) with integer vector atomics; 65 536 bins of each, bin = min(key >> shift, 65535),
+ * shift = max(0, bits - 16), bits = min(32, bits per symbol * k) of the file's head -- the larger of the two files', 32 for a sequence
+ * type that is neither DNA nor AA.  The pass also yields n_w, the most records of one window, and L, the longest record's bytes.
+ * The ranges are then cut greedily from bin 0 upward: a range is closed before the first bin whose addition would take range_bytes
+ * beyond avail; one bin may be a range of its own; one bin that alone exceeds avail is IPKGPU_ERR_NOMEM before any range is loaded,
+ * the message naming the bin's key interval and the bytes it needs.  The first range starts at key 0 and the LAST ENDS AT 2^32
+ * whatever the head says, so a record whose key lies beyond the code space is compared like any other.
+ *
+ * The window.  "db_load_window_bytes" if set; else avail / 16, at least 4 KiB and at most 256 MiB -- with 60 bytes of workspace per
+ * record of at least 16 bytes the fixed part below then stays under a third of avail whatever the files hold.  Per file the window is
+ * at most its body.  Every pass over a file uses the same window, so the cuts, n_w and L are the same on every pass.
+ *
+ * Device memory, a true upper bound of what ipkgpu_mem_stats counts.  m(x) = max(x, 256): a block of the streamed load;
+ * r(x) = max(x rounded up to 256, 256): an array of a database; sort(n) = 9 n + 32768 and scan(n) = n / 8 + 4096 bound rocprim's own
+ * space (the n keys again, digit counters and one look-back state per digit and block; 16 bytes per block of a scan);
+ * scanx(n) = scan(n) * 17 / 16 + 16, for the scans' workspace may be regrown with ensure's margin; pos = 1 for a positioned file.
+ *   ipkgpu_db_stream_window_bytes(W, n_w, L), the fixed part of one file's passes:
+ *       W + 32  +  (L > W ? L + 32 : 0)   the window; a longer record grows it, the old block alive during the copy
+ *       + 3 m(8 n_w) + 4 m(4 n_w) + 3 m(8 (n_w + 1))  +  scanx(n_w + 1)          the per-record workspaces and the windows' scans
+ *     Before a histogram pass n_w and L are bounded from the head: n_w <= min(total k-mers, max(W / 16, 1)),
+ *     L <= min(body, 16 + (8 or 10) * total entries).  fixed = the larger of the two files' figures (one file is streamed at a time).
+ *   db(n, e)    = 3 r(4 n) + r(8 (n + 1)) + r(8 n) + r(8 e) + pos r(4 e)           a resident database
+ *   load(n, e)  = 2 m(8 n) + 2 m(4 n) + m(8 e) + pos m(4 e)                        the kept arrays at their exact size
+ *                 + db(n, e)  +  2 m(8 n) + m(4 n) + m(sort(n))                    behind the last window: the result and the sort
+ *   ipkgpu_db_diff_files_range_bytes(fixed, n_A, e_A, pos_A, n_B, e_B, pos_B, max_records) =
+ *       max( fixed + load(n_A, e_A),   fixed + db(n_A, e_A) + load(n_B, e_B),
+ *            db(n_A, e_A) + db(n_B, e_B) + 8 max(n_A, 1) + 8 (n_A + 1) + 8 max(n_B, 1) + 8 (n_B + 1) + 64 (each workspace 16 at least)
+ *                         + r(16 min(max_records, e_A + e_B)) )                    ipkgpu_db_diff's workspaces and its records
+ *       + scanx(max(n_A, n_B) + 1)
+ * The whole call stays below max over the ranges of range_bytes, and during a histogram pass below
+ *       786 432 (the two histograms)  +  W + 32 + (L > W ? L + 32 : 0) + 2 m(8 n_w) + 2 m(4 n_w).
+ * The histograms are counted by ipkgpu_mem_stats but taken BESIDE "device_budget_bytes": their size does not depend on the files, and a
+ * budget smaller than they are can still be planned.  With expected counts from the histograms every block of a range's loads is
+ * allocated once at its exact size (the kept arrays of ipkgpu_db_load_wanted double when full, up to three times their content while a
+ * copy is in flight); a file that then holds more records or entries in a range than were counted "changed between passes":
+ * IPKGPU_ERR_INVALID, and nothing is written past an allocation.
+ *
+ * Cost: 1 pass over each file when one range fits, else 1 + (number of ranges) passes; a pass is one streamed read of the whole body
+ * with the host's walk, which bounds it.  IPKGPU_ERR_INVALID as in the streamed load: a file the walk refuses (naming the record), a
+ * key in two records of one range, a changed file; on every error everything is given back and the context stays usable.
+ * The last call of a context: ipkgpu_db_diff_files_num_ranges and _range (each range's [lo, hi)); ipkgpu_db_diff_files_stat:
+ * 0 = seconds in all, 1 = in the histogram passes, 2 = in the range loads, 3 = device ms in the diffs (ipkgpu_db_diff_time_ms gives
+ * the same sum), 4 = body bytes read, 5 / 6 = passes over A's / B's body, 7 = seconds in the host's walk, 8 = the window's bytes,
+ * 9 = avail, 10 = n_w, 11 = L.  ipkgpu_db_stream_window_bytes and ipkgpu_db_diff_files_range_bytes are host arithmetic (no GPU). */
+uint64_t ipkgpu_db_stream_window_bytes(uint64_t window, uint64_t n_w, uint64_t longest);
+uint64_t ipkgpu_db_diff_files_range_bytes(uint64_t fixed, uint64_t n_a, uint64_t e_a, int positioned_a, uint64_t n_b, uint64_t e_b,
+                                          int positioned_b, uint64_t max_records);
+int ipkgpu_db_diff_files(ipkgpu_ctx* ctx, const char* path_a, const char* path_b, double eps, ipkgpu_db_diff_counts* counts,
+                         ipkgpu_db_diff_record* records, uint64_t max_records, uint64_t* n_records);
+uint64_t ipkgpu_db_diff_files_num_ranges(const ipkgpu_ctx* ctx);
+int ipkgpu_db_diff_files_range(const ipkgpu_ctx* ctx, uint64_t i, uint64_t* key_lo, uint64_t* key_hi);
+double ipkgpu_db_diff_files_stat(const ipkgpu_ctx* ctx, int which);
 
 #ifdef __cplusplus
 }

@@ -317,22 +317,37 @@ def _g(x):
 @click.option("--eps", type=float, default=1e-2, show_default=True, help="scores match iff |a - b| < eps (the reference's constant, diff.cpp:212)")
 @click.option("--exact", is_flag=True, help="scores match iff their bits are equal (eps = 0)")
 @click.option("--max-records", type=int, default=100, show_default=True, help="with -v: print at most this many pairs (the counts are exact anyway)")
+@click.option("--stream", is_flag=True, help="compare by key ranges, neither file ever on the GPU whole: for files that do not fit device memory")
+@click.option("--budget-mib", type=float, default=None, help="with --stream: the device memory (MiB) the comparison may use on top of what the engine holds [what is free]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
 @click.argument("a", type=click.Path(exists=True, dir_okay=False))
 @click.argument("b", type=click.Path(exists=True, dir_okay=False))
-def diff(verbose, eps, exact, max_records, device, a, b):
+def diff(verbose, eps, exact, max_records, stream, budget_mib, device, a, b):
     """Compares two database files (the reference's ipkdiff): both are loaded onto the GPU and compared there.
 
     Prints the reference's lines in its order, tab separated, each with OK or DIFF and the two values.  Deviations from the
     reference's tool: `Tree index` is really compared (the reference prints ???); `Position support` is printed (commented out there);
     two positioned files also get a `Phylo-k-mer positions` line (equal scores, different positions); the k-mers of the verbose list
     come in ascending order; and the exit status is 1 when any line says DIFF -- the reference's ipkdiff always returns 0
-    (diff.cpp:115-116)."""
+    (diff.cpp:115-116).
+
+    --stream prints the same text and returns the same status without loading either file whole: the head lines come from the files'
+    heads, the comparison from ipkgpu_db_diff_files -- key ranges that each fit the device (or --budget-mib), one histogram pass over
+    each file to plan them and one pass per range (include/ipkgpu.h)."""
     import ipk_amd
+    from ipk_amd import dbfile
+    if budget_mib is not None and not stream:
+        raise click.UsageError("--budget-mib goes with --stream")
+    if budget_mib is not None and not budget_mib > 0:
+        raise click.UsageError("--budget-mib must be positive")
     eng = ipk_amd.Engine(device)
     try:
-        da, db_ = eng.load_db(a), eng.load_db(b)
-        ha, hb = da.header, db_.header
+        if stream:
+            da = db_ = None
+            ha, hb = dbfile.file_info(a), dbfile.file_info(b)
+        else:
+            da, db_ = eng.load_db(a), eng.load_db(b)
+            ha, hb = da.header, db_.header
         all_ok = True
 
         def line(name, va, vb, match=None, show=True):
@@ -354,7 +369,13 @@ def diff(verbose, eps, exact, max_records, device, a, b):
         line("Threshold", log_eps(ha), log_eps(hb), same_omega and ha["kmer_size"] == hb["kmer_size"] and ha["sequence_type"] == hb["sequence_type"])
         line("Reference tree", None, None, ha["newick"] == hb["newick"], show=False)
         line("Tree index", len(ha["tree_index"]), len(hb["tree_index"]), ha["tree_index"] == hb["tree_index"])
-        c, rec = eng.diff_dbs(da, db_, eps=0.0 if exact else eps, max_records=max_records if verbose else 0)
+        if stream:
+            if budget_mib is not None:
+                eng.set_option("release_workspaces", 1)
+                eng.set_option("device_budget_bytes", eng.mem_stats()[0] + int(budget_mib * (1 << 20)))
+            c, rec, _ = eng.diff_files(a, b, eps=0.0 if exact else eps, max_records=max_records if verbose else 0)
+        else:
+            c, rec = eng.diff_dbs(da, db_, eps=0.0 if exact else eps, max_records=max_records if verbose else 0)
         line("Number of k-mers", c["keys_a"], c["keys_b"])
         line("Number of phylo-k-mers", c["entries_a"], c["entries_b"])
         n_diffs = c["entries_only_a"] + c["entries_only_b"] + c["scores_differ"]
@@ -370,26 +391,43 @@ def diff(verbose, eps, exact, max_records, device, a, b):
             for r in rec:
                 kmer = decode_kmer(r["key"], k, st) if st in _ALPHABET else "?"
                 click.echo(f"\t\t{int(r['key'])}\t{kmer}\t{int(r['branch'])}\t{val(r['a_score'])}\t{val(r['b_score'])}\t")
-        da.free(); db_.free()
+        if not stream:
+            da.free(); db_.free()
     finally:
         eng.close()
     sys.exit(0 if all_ok else 1)
 
 
+def _parse_key_range(text):
+    """LO:HI -> (lo, hi): integers (0x.. allowed), 0 <= LO <= HI <= 2^32."""
+    try:
+        lo, hi = (int(x, 0) for x in text.split(":"))
+    except ValueError:
+        raise click.UsageError(f"--key-range takes LO:HI, two integers, not '{text}'")
+    if not 0 <= lo <= hi <= 1 << 32:
+        raise click.UsageError("--key-range needs 0 <= LO <= HI <= 2^32")
+    return lo, hi
+
+
 @ipk.command()
 @click.option("--limit", type=int, default=None, help="print only the first N k-mers of the file [all]")
+@click.option("--key-range", default=None, metavar="LO:HI", help="print only the k-mers with LO <= code < HI, the file streamed through the GPU and never held whole")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
 @click.argument("db", type=click.Path(exists=True, dir_okay=False))
-def dump(limit, device, db):
+def dump(limit, key_range, device, db):
     """Prints a database file as text (the reference's ipkdump), in the file's record order.
 
     Per k-mer one line with the decoded k-mer, then one line per entry: TAB 10^score (as %g) TAB pre-order id of the branch in the
     header's tree (root 0, children in file order), and TAB window position for a positioned file.  A file without a tree in its
-    header (a shard) prints the branch's post-order id as stored."""
+    header (a shard) prints the branch's post-order id as stored.
+
+    --key-range LO:HI prints the records of that key range, in file order among themselves (ipkgpu_db_load_key_range); a file that does
+    not fit device memory is dumped range by range this way.  Its dump as a whole, in file order, is not supported: the file's order
+    is the filter's, not the keys', and no range of keys is a stretch of it."""
     import ipk_amd
     eng = ipk_amd.Engine(device)
     try:
-        d = eng.load_db(db)
+        d = eng.load_db(db, key_range=_parse_key_range(key_range)) if key_range is not None else eng.load_db(db)
         h = d.header
         pre = preorder_ids(h["newick"]) if h["newick"] else None
         keys, off, order = d.keys(), d.key_offsets(), d.filter_order()
@@ -465,20 +503,31 @@ def _check_selection(db_path, mu, omega):
               help="keep only the k-mers these query sequences (FASTA) can look up: the restriction that places them as the whole file does")
 @click.option("--expand-ambiguous", is_flag=True, default=False, help="with --queries: the k-mers `place --expand-ambiguous` looks up")
 @click.option("--strands", type=click.Choice(["given", "both"]), default="given", show_default=True, help="with --queries: the k-mers of both strands")
+@click.option("--key-range", default=None, metavar="LO:HI", help="keep the k-mers with LO <= code < HI, each with every entry (no other selection goes with it)")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, device):
+def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, key_range, device):
     """Writes a selection of a database file as a database file: the first fraction --mu of its k-mers in filter order, of those
     the entries above --omega's threshold (ipkgpu_db_load_select; the definition is in include/ipkgpu.h and is this engine's own --
     the reference's load(file, mu, omega) could not be read).  The file is loaded as far as the selection needs, selected on the GPU
     and written by the device writer; the head is the input's with the new totals and, if given, the new omega.
 
     --queries restricts the selection to the k-mers the reads of a FASTA file can look up (ipkgpu_db_load_wanted: the file is streamed
-    through the GPU in windows and never held whole): `place` of those reads on the output gives what it gives on the input."""
+    through the GPU in windows and never held whole): `place` of those reads on the output gives what it gives on the input.
+
+    --key-range LO:HI writes the records of that key range as a file (ipkgpu_db_load_key_range, streamed the same way)."""
     import ipk_amd
     from ipk_amd import dbfile
+    if key_range is not None and (mu is not None or omega is not None or queries is not None):
+        raise click.UsageError("--key-range goes with no other selection")
     _check_selection(db_path, mu, omega)
     eng = ipk_amd.Engine(device)
     try:
+        if key_range is not None:
+            d = eng.load_db(db_path, key_range=_parse_key_range(key_range))
+            dbfile.write_db_device(eng, d, output, **dbfile.header_args(d.header))
+            click.echo(f"Output: {output} ({d.num_keys} k-mers, {d.num_entries} entries)")
+            d.free()
+            return
         wanted = None
         if queries is not None:
             info = dbfile.file_info(db_path)

@@ -9,6 +9,9 @@
 // on the device.  A record longer than the window finds it empty, grows the block and is a window of its own.  Behind the last window: the sort of (key, kept index),
 // the arrays in key order, the entries gathered from file order into key order; then the selection at min_log_score over the result.
 // Every temporary is taken through dev_malloc and given back before the call returns; the kept arrays double when they are full.
+// The same load with a second predicate, a key range in place of the set, is ipkgpu_db_load_key_range; with the kept counts known
+// beforehand (StreamKeep::expected) every block is taken once at its exact size; and without an output it is the histogram pass of
+// ipkgpu_db_diff_files (db_diff_files.hpp), which keeps nothing.
 #pragma once
 
 namespace {
@@ -20,11 +23,18 @@ struct StreamBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-int stream_grow(ipkgpu_ctx* ctx, StreamBuf& b, size_t used, size_t need, const char* what)
+// exact: the block gets what is asked for and no more, and a block with nothing to keep is given back before the new one is taken (the
+// loads whose sizes are known beforehand: their peak is the sum of what they hold, ipkgpu_db_diff_files plans by it)
+int stream_grow(ipkgpu_ctx* ctx, StreamBuf& b, size_t used, size_t need, const char* what, bool exact = false)
 {
     if (need <= b.cap && b.p) return IPKGPU_OK;
     need = std::max<size_t>(need, 256);
-    size_t want = std::max(need, b.cap * 2);
+    size_t want = exact ? need : std::max(need, b.cap * 2);
+    if (exact && b.p && !used) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)dev_free(ctx, b.p, b.cap);
+        b.p = nullptr; b.cap = 0;
+    }
     void* q = nullptr;
     hipError_t e = dev_malloc(ctx, &q, want);
     if (e != hipSuccess && want > need) { (void)hipGetLastError(); want = need; e = dev_malloc(ctx, &q, want); }
@@ -44,17 +54,36 @@ int stream_grow(ipkgpu_ctx* ctx, StreamBuf& b, size_t used, size_t need, const c
     return IPKGPU_OK;
 }
 
-// R(prefix, K): the first min(keep_records, header total) records of the file restricted to the keys of `set`, every kept key with all
-// its entries, as a database with the head of the file (totals replaced).  t_load[8] = windows, [9] = records kept.
-int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set, uint64_t keep_records, ipkgpu_db** out)
+// What a streamed pass over a file keeps, and what is known about the file beforehand.
+struct StreamKeep {
+    const ipkgpu_kmer_set* set = nullptr;        // the records whose key the set names (ipkgpu_db_load_wanted); without a set:
+    uint64_t key_lo = 0, key_hi = 0;             // those with key_lo <= key < key_hi (ipkgpu_db_load_key_range)
+    // expected: the kept records and entries are known (a histogram pass counted them).  The kept arrays are then allocated once at
+    // that size, every other block at exactly what it needs; a file that holds more "changed between passes".
+    bool expected = false;
+    uint64_t exp_records = 0, exp_entries = 0;
+    uint64_t window = 0;                         // the window's bytes (0: "db_load_window_bytes", or DB_STREAM_WINDOW)
+    // in: the most records of one window and the longest record's bytes where a pass before has seen them (0: not known);
+    // out: what this pass saw
+    uint64_t n_w = 0, longest = 0;
+    // the histogram pass (out == nullptr): nothing is kept; per window db_stream_hist_kernel over the heads
+    uint32_t* rec_hist = nullptr; unsigned long long* ent_hist = nullptr; uint32_t shift = 0;
+};
+
+// R(prefix, K): the first min(keep_records, header total) records of the file restricted to the keys of keep.set (or of the key range),
+// every kept key with all its entries, as a database with the head of the file (totals replaced).  t_load[8] = windows, [9] = records
+// kept.  out == nullptr: the histogram pass.
+int db_stream_load(ipkgpu_ctx* ctx, const char* path, StreamKeep& keep, uint64_t keep_records, ipkgpu_db** out)
 {
+    const ipkgpu_kmer_set* set = keep.set;
+    const bool hist = out == nullptr, exact = keep.expected || hist;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     ipkgpu_db_file* file = nullptr;
     if (const int rc = ipkgpu_db_file_open(path, &file)) return fail(ctx, rc, "%s", ipkgpu_db_file_last_error());
     struct FileGuard { ipkgpu_db_file* f; ~FileGuard() { ipkgpu_db_file_close(f); } } fguard{file};
     ipkfmt::Head& hd = file->head;
-    RC_TRY(set_fits(ctx, set, file));
+    if (set) RC_TRY(set_fits(ctx, set, file));
     const bool whole = keep_records >= hd.total_kmers;
     const uint64_t n_total = hd.total_kmers, ne_total = hd.total_entries;
     const uint64_t body = file->body_bytes();
@@ -75,29 +104,35 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
     const uint64_t chunk = std::min<uint64_t>(ctx->opt_load_chunk > 0 ? (uint64_t)ctx->opt_load_chunk : SPILL_STAGE, SPILL_STAGE);
     // the window's capacity in record bytes; the block has 16 bytes more for the head a chunk may end in, and 16 for the aligned dwords
     // the positioned entries are read as (the last one two bytes past its end)
-    const uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(ctx->opt_load_window > 0 ? (uint64_t)ctx->opt_load_window : DB_STREAM_WINDOW, body), ipkfmt::RECORD_HEAD_BYTES);
+    const uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(keep.window ? keep.window : ctx->opt_load_window > 0 ? (uint64_t)ctx->opt_load_window : DB_STREAM_WINDOW, body),
+                                            ipkfmt::RECORD_HEAD_BYTES);
     constexpr uint64_t WIN_SLACK = 32;
     ipkfmt::RecordWalker walk;
     walk.begin(hd.body_at, body, positioned, n_total, whole ? ~(uint64_t)0 : keep_records);
     double t_read = 0, t_walk = 0, t_wait = 0, t_device = 0;
-    uint64_t bytes_read = 0, w_lo = 0, r0 = 0, r_seen = 0, kept = 0, kept_e = 0, n_windows = 0;
+    uint64_t bytes_read = 0, w_lo = 0, r0 = 0, r_seen = 0, kept = 0, kept_e = 0, n_windows = 0, seen_n_w = 0, seen_longest = 0;
     std::vector<uint64_t> rel;
+    const uint64_t n_w_first = std::min<uint64_t>(keep.n_w, n_total);      // (a window has at most the file's records, whatever the caller says)
 
     // the records [r0, r1) of the window that starts at body offset w_lo: their wanted ones to the end of the kept arrays
     auto process = [&](uint64_t r1) -> int {
         const uint64_t nw = r1 - r0;
         if (nw == 0) return IPKGPU_OK;
         const auto t0 = std::chrono::steady_clock::now();
-        RC_TRY(stream_grow(ctx, w_starts, 0, nw * 8, "a window's record starts"));
-        RC_TRY(stream_grow(ctx, w_sk, 0, nw * 8, "a window's keys"));
-        RC_TRY(stream_grow(ctx, w_fvb, 0, nw * 4, "a window's filter values"));
-        RC_TRY(stream_grow(ctx, w_cnt, 0, nw * 4, "a window's counts"));
-        RC_TRY(stream_grow(ctx, w_flag, 0, nw * 4, "a window's flags"));
-        RC_TRY(stream_grow(ctx, w_cntw, 0, nw * 4, "a window's wanted counts"));
-        RC_TRY(stream_grow(ctx, w_fscan, 0, (nw + 1) * 8, "a window's flag scan"));
-        RC_TRY(stream_grow(ctx, w_cscan, 0, (nw + 1) * 8, "a window's count scan"));
-        RC_TRY(stream_grow(ctx, w_segd, 0, (nw + 1) * 8, "a window's segments"));
-        RC_TRY(stream_grow(ctx, w_segs, 0, nw * 8, "a window's segments"));
+        seen_n_w = std::max(seen_n_w, nw);
+        const uint64_t na = std::max(nw, n_w_first);                         // (the workspaces at once at the known most, where it is known)
+        RC_TRY(stream_grow(ctx, w_starts, 0, na * 8, "a window's record starts", exact));
+        RC_TRY(stream_grow(ctx, w_sk, 0, na * 8, "a window's keys", exact));
+        RC_TRY(stream_grow(ctx, w_fvb, 0, na * 4, "a window's filter values", exact));
+        RC_TRY(stream_grow(ctx, w_cnt, 0, na * 4, "a window's counts", exact));
+        if (!hist) {
+            RC_TRY(stream_grow(ctx, w_flag, 0, na * 4, "a window's flags", exact));
+            RC_TRY(stream_grow(ctx, w_cntw, 0, na * 4, "a window's wanted counts", exact));
+            RC_TRY(stream_grow(ctx, w_fscan, 0, (na + 1) * 8, "a window's flag scan", exact));
+            RC_TRY(stream_grow(ctx, w_cscan, 0, (na + 1) * 8, "a window's count scan", exact));
+            RC_TRY(stream_grow(ctx, w_segd, 0, (na + 1) * 8, "a window's segments", exact));
+            RC_TRY(stream_grow(ctx, w_segs, 0, na * 8, "a window's segments", exact));
+        }
         try { rel.resize(nw); } catch (const std::bad_alloc&) { return fail(ctx, IPKGPU_ERR_NOMEM, "out of host memory"); }
         for (uint64_t i = 0; i < nw; ++i) rel[i] = walk.starts[r0 + i] - w_lo;
         HIP_TRY(ctx, hipMemcpyAsync(w_starts.p, rel.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -107,8 +142,19 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
                                            w_sk.as<unsigned long long>(), w_fvb.as<uint32_t>(), w_cnt.as<uint32_t>());
         else hipLaunchKernelGGL(db_unpack_heads_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, image, w_starts.as<uint64_t>(), nw,
                                 w_sk.as<unsigned long long>(), w_fvb.as<uint32_t>(), w_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(db_stream_flag_kernel, dim3(nb), dim3(256), 0, ctx->stream, w_sk.as<unsigned long long>(), w_cnt.as<uint32_t>(), nw, set->d_words,
-                           set->n_codes, w_flag.as<uint32_t>(), w_cntw.as<uint32_t>());
+        if (hist) {
+            hipLaunchKernelGGL(db_stream_hist_kernel, dim3(nb), dim3(256), 0, ctx->stream, w_sk.as<unsigned long long>(), w_cnt.as<uint32_t>(), nw, keep.shift,
+                               keep.rec_hist, keep.ent_hist);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                 // (`rel` is written again for the next window)
+            ++n_windows;
+            t_device += since(t0);
+            return IPKGPU_OK;
+        }
+        if (set) hipLaunchKernelGGL(db_stream_flag_kernel, dim3(nb), dim3(256), 0, ctx->stream, w_sk.as<unsigned long long>(), w_cnt.as<uint32_t>(), nw, set->d_words,
+                                    set->n_codes, w_flag.as<uint32_t>(), w_cntw.as<uint32_t>());
+        else hipLaunchKernelGGL(db_stream_flag_range_kernel, dim3(nb), dim3(256), 0, ctx->stream, w_sk.as<unsigned long long>(), w_cnt.as<uint32_t>(), nw, keep.key_lo,
+                                keep.key_hi, w_flag.as<uint32_t>(), w_cntw.as<uint32_t>());
         HIP_TRY(ctx, hipGetLastError());
         RC_TRY(scan_u32(ctx, w_flag.as<uint32_t>(), nw, w_fscan.as<uint64_t>()));
         RC_TRY(scan_u32(ctx, w_cntw.as<uint32_t>(), nw, w_cscan.as<uint64_t>()));
@@ -120,6 +166,10 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
         if (kw > nw || ew > win.cap / entry_bytes)
             return fail(ctx, IPKGPU_ERR_HIP, "%s: a window's scans disagree with the walk: %llu records and %llu entries wanted of %llu records", path,
                         (unsigned long long)kw, (unsigned long long)ew, (unsigned long long)nw);
+        // (with expected counts the kept arrays have exactly that room: nothing is written beyond it)
+        if (keep.expected && (kept + kw > keep.exp_records || kept_e + ew > keep.exp_entries))
+            return fail(ctx, IPKGPU_ERR_INVALID, "%s: the file changed between passes: more than the %llu records and %llu entries counted before have keys in [%llu, %llu)",
+                        path, (unsigned long long)keep.exp_records, (unsigned long long)keep.exp_entries, (unsigned long long)keep.key_lo, (unsigned long long)keep.key_hi);
         if (kw) {
             RC_TRY(stream_grow(ctx, k_sk, kept * 8, (kept + kw) * 8, "the kept keys"));
             RC_TRY(stream_grow(ctx, k_fvb, kept * 4, (kept + kw) * 4, "the kept filter values"));
@@ -154,7 +204,17 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
         setvbuf(fh, nullptr, _IONBF, 0);
         if (fseeko(fh, (off_t)hd.body_at, SEEK_SET) != 0) return fail(ctx, IPKGPU_ERR_INVALID, "%s: seek failed", path);
         RC_TRY(spill_stage(ctx, (size_t)std::min<uint64_t>(chunk, std::max<uint64_t>(body, 1))));
-        if (body && keep_records) RC_TRY(stream_grow(ctx, win, 0, cap + WIN_SLACK, "the window"));
+        if (body && keep_records) RC_TRY(stream_grow(ctx, win, 0, std::max(cap, std::min(keep.longest, body)) + WIN_SLACK, "the window", exact));
+        if (keep.expected && keep.exp_records) {                             // the kept arrays, once
+            RC_TRY(stream_grow(ctx, k_sk, 0, keep.exp_records * 8, "the kept keys", true));
+            RC_TRY(stream_grow(ctx, k_fvb, 0, keep.exp_records * 4, "the kept filter values", true));
+            RC_TRY(stream_grow(ctx, k_cnt, 0, keep.exp_records * 4, "the kept counts", true));
+            RC_TRY(stream_grow(ctx, k_eoff, 0, keep.exp_records * 8, "the kept entry offsets", true));
+            if (keep.exp_entries) {
+                RC_TRY(stream_grow(ctx, k_ent, 0, keep.exp_entries * 8, "the kept entries", true));
+                if (positioned) RC_TRY(stream_grow(ctx, k_pos, 0, keep.exp_entries * 4, "the kept positions", true));
+            }
+        }
         uint64_t j = 0;
         for (uint64_t lo = 0; lo < body && keep_records && !(walk.done() && lo >= walk.pos); lo += chunk, ++j) {
             const uint64_t hi = std::min(body, lo + chunk);
@@ -179,6 +239,7 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
             };
             for (uint64_t r = r_seen; r < walk.starts.size(); ++r) {
                 const uint64_t s = walk.starts[r], e = r + 1 < walk.starts.size() ? walk.starts[r + 1] : walk.pos;
+                seen_longest = std::max(seen_longest, e - s);
                 if (e - w_lo <= cap) continue;
                 if (r > r0) {                                                // the window is closed at this record's start
                     RC_TRY(to_window(s));
@@ -189,7 +250,7 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
                 }
                 // one record longer than the window, which is empty: the block grows to hold it (and stays so); the record is a window of
                 // its own, for the cuts go on by "db_load_window_bytes"
-                RC_TRY(stream_grow(ctx, win, (size_t)(cur > w_lo ? cur - w_lo : 0), (size_t)(e - w_lo + WIN_SLACK), "the window (one record is longer than it)"));
+                RC_TRY(stream_grow(ctx, win, (size_t)(cur > w_lo ? cur - w_lo : 0), (size_t)(e - w_lo + WIN_SLACK), "the window (one record is longer than it)", exact));
             }
             r_seen = walk.starts.size();
             RC_TRY(to_window(walk.done() ? std::min(hi, walk.pos) : hi));
@@ -203,6 +264,14 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
                     (unsigned long long)keep_records);
     }
     RC_TRY(process(walk.starts.size()));
+    keep.n_w = seen_n_w; keep.longest = seen_longest;
+    auto times = [&]() {
+        ctx->t_load[1] = t_read; ctx->t_load[2] = t_walk; ctx->t_load[3] = t_wait;
+        ctx->t_load[4] = 0; ctx->t_load[5] = 0; ctx->t_load[6] = t_device * 1e3;
+        ctx->t_load[7] = (double)bytes_read; ctx->t_load[8] = (double)n_windows; ctx->t_load[9] = (double)kept;
+        ctx->t_load[0] = since(t_begin);
+    };
+    if (hist) { times(); return IPKGPU_OK; }
     if ((kept_e + DB_UNPACK_TILE - 1) / DB_UNPACK_TILE > 0x7FFFFFFFull) return fail(ctx, IPKGPU_ERR_INVALID, "%s: too many entries for one launch", path);
 
     // the kept heads into key order, the kept entries behind them
@@ -215,14 +284,14 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
     if (kept == 0) {
         HIP_TRY(ctx, hipMemsetAsync(db->d_key_off, 0, 8, ctx->stream));
     } else {
-        RC_TRY(stream_grow(ctx, s_sorted, 0, kept * 8, "the sorted keys"));
-        RC_TRY(stream_grow(ctx, s_cnt, 0, kept * 4, "the counts in key order"));
-        RC_TRY(stream_grow(ctx, s_src, 0, kept * 8, "the entry offsets in key order"));
+        RC_TRY(stream_grow(ctx, s_sorted, 0, kept * 8, "the sorted keys", exact));
+        RC_TRY(stream_grow(ctx, s_cnt, 0, kept * 4, "the counts in key order", exact));
+        RC_TRY(stream_grow(ctx, s_src, 0, kept * 8, "the entry offsets in key order", exact));
         uint32_t* d_dup = small_at(ctx, SMALL_REC_BIG);
         HIP_TRY(ctx, hipMemsetAsync(d_dup, 0, 4, ctx->stream));
         size_t tmp_bytes = 0;
         HIP_TRY(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, k_sk.as<unsigned long long>(), s_sorted.as<unsigned long long>(), (size_t)kept, 0, 64, ctx->stream));
-        RC_TRY(stream_grow(ctx, s_tmp, 0, tmp_bytes, "the sort's workspace"));
+        RC_TRY(stream_grow(ctx, s_tmp, 0, tmp_bytes, "the sort's workspace", exact));
         HIP_TRY(ctx, rocprim::radix_sort_keys(s_tmp.p, tmp_bytes, k_sk.as<unsigned long long>(), s_sorted.as<unsigned long long>(), (size_t)kept, 0, 64, ctx->stream));
         const uint32_t nb = (uint32_t)((kept + 255) / 256);
         hipLaunchKernelGGL(db_load_order_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, s_sorted.as<unsigned long long>(), k_eoff.as<uint64_t>(), k_fvb.as<uint32_t>(),
@@ -252,10 +321,7 @@ int db_stream_load(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_set* set
     file->file_bytes = hd.body_at + ipkfmt::RECORD_HEAD_BYTES * kept + entry_bytes * kept_e;
     file->walked = true; file->n_records = kept; file->n_entries = kept_e; file->max_count = walk.max_count;
     db->file = file; fguard.f = nullptr;
-    ctx->t_load[1] = t_read; ctx->t_load[2] = t_walk; ctx->t_load[3] = t_wait;
-    ctx->t_load[4] = 0; ctx->t_load[5] = 0; ctx->t_load[6] = t_device * 1e3;
-    ctx->t_load[7] = (double)bytes_read; ctx->t_load[8] = (double)n_windows; ctx->t_load[9] = (double)kept;
-    ctx->t_load[0] = since(t_begin);
+    times();
     guard.r = nullptr;
     *out = db;
     return IPKGPU_OK;
@@ -273,7 +339,9 @@ int ipkgpu_db_load_wanted(ipkgpu_ctx* ctx, const char* path, const ipkgpu_kmer_s
     if (!set || set->ctx != ctx) return fail(ctx, IPKGPU_ERR_INVALID, "a k-mer set of this context is needed");
     if (min_log_score != min_log_score) return fail(ctx, IPKGPU_ERR_INVALID, "min_log_score is NaN");
     ipkgpu_db* restricted = nullptr;
-    RC_TRY(db_stream_load(ctx, path, set, keep_kmers, &restricted));
+    StreamKeep keep;
+    keep.set = set;
+    RC_TRY(db_stream_load(ctx, path, keep, keep_kmers, &restricted));
     // the selection's steps 2 and 3 over the kept records (every one a candidate): entries at or below the score go, and keys left without one
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = db_select(ctx, restricted, ~(uint64_t)0, min_log_score, out);

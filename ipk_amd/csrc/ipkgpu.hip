@@ -181,6 +181,8 @@ struct ipkgpu_ctx {
     int64_t opt_load_window = 0;         // "db_load_window_bytes": bytes of the device window of ipkgpu_db_load_wanted (0: DB_STREAM_WINDOW)
     double t_load[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_load / _load_select / _load_wanted (ipkgpu_db_load_time), t_diff_ms: last ipkgpu_db_diff
     double t_diff_ms = 0;
+    std::vector<uint64_t> dfiles_ranges;     // last ipkgpu_db_diff_files: lo, hi of every range; dfiles_stat: ipkgpu_db_diff_files_stat
+    double dfiles_stat[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double t_select_ms = 0;              // device time of the last ipkgpu_db_select (ipkgpu_db_select_time_ms)
     // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
     // place_amb: the per-window tables of ambiguous windows (ipkgpu_db_place_opts)
@@ -3446,4 +3448,5 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 #include "db_place.hpp"
 #include "db_kmerset.hpp"
 #include "db_stream.hpp"
+#include "db_diff_files.hpp"
 #include "comm_rccl.hpp"

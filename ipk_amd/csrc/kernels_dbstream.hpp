@@ -10,13 +10,17 @@
 //                             db_unpack_entries_kernel, which then appends the wanted entries by entry ranges, as it is
 // After the last window the kept heads are sorted by (key, kept index) and db_load_order_kernel<false> makes the arrays in key order;
 //   db_stream_gather_kernel   per ENTRY: kept entries from file order into key order, by db_unpack_entries_kernel's tile scheme
-// No output place comes from an atomic: the kept records keep the file's order, the result is the same bits on every run.
+// ipkgpu_db_load_key_range takes db_stream_flag_range_kernel (key_lo <= key < key_hi) in place of the bitmap test.  The histogram pass
+// of ipkgpu_db_diff_files keeps nothing: behind the heads only db_stream_hist_kernel, records and entries per key bin.
+// No output place comes from an atomic: the kept records keep the file's order, the result is the same bits on every run (the
+// histogram's integer sums do not depend on the order of their atomics either).
 #pragma once
 #include "kernels_dbselect.hpp"
 
 namespace ipkgpu {
 
 constexpr uint64_t DB_STREAM_WINDOW = (uint64_t)256 << 20;           // bytes of the device window when "db_load_window_bytes" is 0
+constexpr uint32_t DB_HIST_BINS = 1u << 16;                          // key bins of ipkgpu_db_diff_files' histogram pass
 
 __global__ __launch_bounds__(256) void db_stream_flag_kernel(const unsigned long long* __restrict__ sortkey, const uint32_t* __restrict__ counts, uint64_t n,
                                                              const uint32_t* __restrict__ bitmap, uint64_t n_codes, uint32_t* __restrict__ flag,
@@ -27,6 +31,35 @@ __global__ __launch_bounds__(256) void db_stream_flag_kernel(const unsigned long
     const bool w = db_key_wanted(bitmap, n_codes, (uint32_t)(sortkey[i] >> 32));
     flag[i] = w ? 1u : 0u;
     cnt_wanted[i] = w ? counts[i] : 0u;
+}
+
+// The second predicate of the streamed load (ipkgpu_db_load_key_range): wanted = key_lo <= key < key_hi, in 64 bits (key_hi may be
+// 2^32).  A kernel of its own, so that the bitmap path above compiles to what it was.
+__global__ __launch_bounds__(256) void db_stream_flag_range_kernel(const unsigned long long* __restrict__ sortkey, const uint32_t* __restrict__ counts, uint64_t n,
+                                                                   uint64_t key_lo, uint64_t key_hi, uint32_t* __restrict__ flag,
+                                                                   uint32_t* __restrict__ cnt_wanted)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = (uint64_t)(sortkey[i] >> 32);
+    const bool w = key >= key_lo && key < key_hi;
+    flag[i] = w ? 1u : 0u;
+    cnt_wanted[i] = w ? counts[i] : 0u;
+}
+
+// The histogram pass of ipkgpu_db_diff_files: one thread per record of the window; bin = min(key >> shift, DB_HIST_BINS - 1).
+// rec_hist[bin] += 1, ent_hist[bin] += the record's entry count: integer vector atomics in global memory (sums of integers: the same
+// totals on every run whatever the order).  Both histograms have DB_HIST_BINS elements; the bin is clamped before it indexes.
+__global__ __launch_bounds__(256) void db_stream_hist_kernel(const unsigned long long* __restrict__ sortkey, const uint32_t* __restrict__ counts, uint64_t n,
+                                                             uint32_t shift, uint32_t* __restrict__ rec_hist, unsigned long long* __restrict__ ent_hist)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = (uint32_t)(sortkey[i] >> 32);
+    const uint32_t bin = min(key >> shift, DB_HIST_BINS - 1);
+    atomicAdd(&rec_hist[bin], 1u);
+    const uint32_t c = counts[i];
+    if (c) atomicAdd(&ent_hist[bin], (unsigned long long)c);
 }
 
 // f_scan, c_scan: the exclusive scans of flag and cnt_wanted, n + 1 values each.  kept_base, entry_base: the kept records and entries

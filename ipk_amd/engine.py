@@ -961,17 +961,30 @@ def _select_time_ms(self):
     return float(self._lib.ipkgpu_db_select_time_ms(self._h))
 
 
-def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=None, wanted=None):
+def _load_db(self, path, mu=None, omega=None, keep_kmers=None, min_log_score=None, wanted=None, key_range=None):
     """ipkgpu_db_load: a database file onto the device -- the Db the builds produce, with the file's filter values and record order
     (filter_values(), filter_order()) and `.header`, the dict dbfile.read_db returns for the file's head.
     dbfile.write_db_device(engine, db, path, **dbfile.header_args(db.header)) gives the file back byte for byte.
     With mu, omega, keep_kmers or min_log_score: ipkgpu_db_load_select -- select_db(load_db(path), ...) array for array, reading only the
     prefix of the file that holds the first k-mers asked for (mu counts against the header's total).
     With wanted= (a KmerSet of Engine.kmer_set): ipkgpu_db_load_wanted -- select_db(load_db(path, ...), wanted=wanted) array for array, the
-    file streamed through a device window of option "db_load_window_bytes" and never held whole: for a file larger than device memory."""
+    file streamed through a device window of option "db_load_window_bytes" and never held whole: for a file larger than device memory.
+    With key_range=(lo, hi): ipkgpu_db_load_key_range -- the records with lo <= key < hi (hi at most 2^32), every one with all its entries,
+    through the same streamed load; no other selection goes with it."""
     from . import dbfile
     _bind_keymajor(self._lib)
     out = C.c_void_p()
+    if key_range is not None:
+        if wanted is not None or mu is not None or omega is not None or keep_kmers is not None or min_log_score is not None:
+            raise ValueError("key_range= goes with no other selection")
+        _bind_diff_files(self._lib)
+        lo, hi = (int(x) for x in key_range)
+        if lo < 0 or hi < 0 or hi >= 1 << 64:
+            raise ValueError("key_range is (lo, hi) with 0 <= lo <= hi <= 2^32")
+        rc = self._lib.ipkgpu_db_load_key_range(self._h, os.fsencode(path), lo, hi, C.byref(out))
+        if rc != 0:
+            raise self._err(rc)
+        return _finish_selection(self, out, None)
     if wanted is not None:
         _bind_stream(self._lib)
         head = dbfile.file_info(path)
@@ -1025,6 +1038,87 @@ def _diff_time_ms(self):
     return float(self._lib.ipkgpu_db_diff_time_ms(self._h))
 
 
+# ---- two files compared by key ranges (ipkgpu_db_diff_files) ---------------------------------------------------------------------------
+
+ABI_SYMBOLS += [
+    "ipkgpu_db_load_key_range", "ipkgpu_db_diff_files", "ipkgpu_db_diff_files_num_ranges", "ipkgpu_db_diff_files_range",
+    "ipkgpu_db_diff_files_stat", "ipkgpu_db_diff_files_range_bytes", "ipkgpu_db_stream_window_bytes",
+]
+
+DIFF_FILES_STATS = ("total_s", "hist_s", "loads_s", "diff_ms", "body_bytes_read", "passes_a", "passes_b", "walk_s", "window_bytes", "avail_bytes",
+                    "max_window_records", "longest_record_bytes")
+
+
+def _bind_diff_files(L):
+    if getattr(L, "_diff_files_bound", False):
+        return
+    L.ipkgpu_db_load_key_range.restype = C.c_int
+    L.ipkgpu_db_load_key_range.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_diff_files.restype = C.c_int
+    L.ipkgpu_db_diff_files.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_double, C.POINTER(DiffCounts), C.c_void_p, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]
+    L.ipkgpu_db_diff_files_num_ranges.restype = C.c_uint64
+    L.ipkgpu_db_diff_files_num_ranges.argtypes = [C.c_void_p]
+    L.ipkgpu_db_diff_files_range.restype = C.c_int
+    L.ipkgpu_db_diff_files_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ipkgpu_db_diff_files_stat.restype = C.c_double
+    L.ipkgpu_db_diff_files_stat.argtypes = [C.c_void_p, C.c_int]
+    L.ipkgpu_db_diff_files_range_bytes.restype = C.c_uint64
+    L.ipkgpu_db_diff_files_range_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64]
+    L.ipkgpu_db_stream_window_bytes.restype = C.c_uint64
+    L.ipkgpu_db_stream_window_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+    L._diff_files_bound = True
+
+
+def stream_window_bytes(window, n_w, longest):
+    """ipkgpu_db_stream_window_bytes: the fixed device bytes of one file's streamed passes (the formula of include/ipkgpu.h; no GPU)."""
+    L = load_library()
+    _bind_diff_files(L)
+    return int(L.ipkgpu_db_stream_window_bytes(int(window), int(n_w), int(longest)))
+
+
+def diff_files_range_bytes(fixed, n_a, e_a, positioned_a, n_b, e_b, positioned_b, max_records=0):
+    """ipkgpu_db_diff_files_range_bytes: the peak device bytes of comparing one key range (the formula of include/ipkgpu.h; no GPU)."""
+    L = load_library()
+    _bind_diff_files(L)
+    return int(L.ipkgpu_db_diff_files_range_bytes(int(fixed), int(n_a), int(e_a), int(bool(positioned_a)), int(n_b), int(e_b), int(bool(positioned_b)),
+                                                  int(max_records)))
+
+
+def _diff_files_info(self):
+    """The engine's last diff_files: "ranges" [(lo, hi)] and the figures of DIFF_FILES_STATS (ipkgpu_db_diff_files_stat)."""
+    _bind_diff_files(self._lib)
+    info = {k: float(self._lib.ipkgpu_db_diff_files_stat(self._h, i)) for i, k in enumerate(DIFF_FILES_STATS)}
+    for k in DIFF_FILES_STATS[4:7] + DIFF_FILES_STATS[8:]:
+        info[k] = int(info[k])
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    info["ranges"] = []
+    for i in range(int(self._lib.ipkgpu_db_diff_files_num_ranges(self._h))):
+        self._lib.ipkgpu_db_diff_files_range(self._h, i, C.byref(lo), C.byref(hi))
+        info["ranges"].append((int(lo.value), int(hi.value)))
+    return info
+
+
+def _diff_files(self, a, b, eps=1e-2, max_records=0):
+    """ipkgpu_db_diff_files: diff_dbs(load_db(a), load_db(b), eps, max_records) field for field, for files that do not fit device memory
+    together -- compared by key ranges planned against "device_budget_bytes" (or the device's free memory).  Returns (counts, records,
+    info); info: _diff_files_info's dict (the ranges, the passes over each body, seconds and bytes)."""
+    _bind_keymajor(self._lib)
+    _bind_diff_files(self._lib)
+    counts = DiffCounts()
+    rec = np.zeros(max(int(max_records), 1), DIFF_RECORD)
+    n = C.c_uint64(0)
+    rc = self._lib.ipkgpu_db_diff_files(self._h, os.fsencode(a), os.fsencode(b), float(eps), C.byref(counts), rec.ctypes.data, int(max_records),
+                                        C.byref(n))
+    if rc != 0:
+        raise self._err(rc)
+    d = {name: int(getattr(counts, name)) for name, _ in DiffCounts._fields_[:-1]}
+    d["max_abs_diff"] = float(counts.max_abs_diff)
+    return d, rec[:int(n.value)].copy(), _diff_files_info(self)
+
+
+Engine.diff_files = _diff_files
+Engine.diff_files_info = _diff_files_info
 Engine.load_db = _load_db
 Engine.select_db = _select_db
 Engine.select_time_ms = _select_time_ms
