@@ -106,7 +106,8 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * allocations from estimates, no key list inside the scoring call; 7 / 8: the quad kernel's workgroups never / always draw
  * their tiles; 9 / 10: the dense key-major writer with tile-by-tile / with line-cut stores whatever the group count; 11: 128-KB
  * table slices reduced by the workgroup-per-slice kernel instead of the persistent one; 12 / 13: the compressed key-major writer
- * per key block / per run of key blocks whatever the group count; 14: the line-cut writer's stores all plain, none non-temporal),
+ * per key block / per run of key blocks whatever the group count; 14: the line-cut writer's stores all plain, none non-temporal;
+ * 15: the dense table slices of the 6-byte-pair reduce (DNA k = 8..10) leave by plain stores, not non-temporal ones),
  * "debug_pool_chunks", "debug_pool_limit_bytes",
  * "debug_wg_chunks2", "debug_rounds", "debug_kmc_pass" (groups per pass of the compressed key-major writer),
  * "debug_prefix_mats" (matrices per workgroup of the prefix-sum kernel: 1, 2, 4, 8; 0 = by the matrix count) (diagnostics and tests only);

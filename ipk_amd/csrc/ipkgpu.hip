@@ -762,9 +762,12 @@ int launch_stream_pass2(ipkgpu_ctx* ctx, uint32_t n_gb, uint64_t T, uint32_t* ta
         }
         if (layout == PairLayout::PAIR6) {
             // (the one (sigma, k) family whose pass 1 writes the layout: no other instantiation of the PAIR6 reduce exists)
-            if constexpr (quad_layout<SIGMA, K>() == PairLayout::PAIR6)
-                return compress ? launch(reduce_buckets_kernel<TBL, NT, true, PairLayout::PAIR6>) : launch(reduce_buckets_kernel<TBL, NT, false, PairLayout::PAIR6>);
-            else
+            if constexpr (quad_layout<SIGMA, K>() == PairLayout::PAIR6) {
+                if (compress) return launch(reduce_buckets_kernel<TBL, NT, true, PairLayout::PAIR6>);
+                // (dense slices leave by non-temporal stores; debug_flags bit 15: the plain stores they replaced, for the comparison)
+                return (ctx->opt_flags & 32768) ? launch(reduce_buckets_kernel<TBL, NT, false, PairLayout::PAIR6, false>)
+                                                : launch(reduce_buckets_kernel<TBL, NT, false, PairLayout::PAIR6, true>);
+            } else
                 return fail(ctx, IPKGPU_ERR_INVALID, "no 6-byte pair layout for this sigma/k");
         }
         return compress ? launch(reduce_buckets_kernel<TBL, NT, true>) : launch(reduce_buckets_kernel<TBL, NT, false>);

@@ -1193,7 +1193,9 @@ __device__ __forceinline__ uint2 pool_load(const uint2* p)
 // dwordx2 of their slots, half a load instruction per pair instead of one -- and the slot IS the table index.  A load is issued
 // where its first pair exists (index < n); the chunk's bytes behind n are allocated but hold nothing, and every pair is tested
 // against n again before it reaches the table.
-template <uint32_t TBL, int NT, bool COMPRESS = false, PairLayout LAYOUT = PairLayout::PAIR8>
+// NTS: the dense slice leaves by non-temporal stores -- whole, aligned lines, written once and read next by the key-major writer
+// gigabytes later (cfg2 reduce: 3.46-3.53 ms against 3.69-3.71 with plain stores).
+template <uint32_t TBL, int NT, bool COMPRESS = false, PairLayout LAYOUT = PairLayout::PAIR8, bool NTS = false>
 __global__ __launch_bounds__(NT) void reduce_buckets_kernel(const uint2* __restrict__ pool,
                                                            const uint64_t* __restrict__ off, const uint2* __restrict__ list,
                                                            uint32_t NB, uint64_t T, uint32_t* __restrict__ table,
@@ -1294,6 +1296,10 @@ __global__ __launch_bounds__(NT) void reduce_buckets_kernel(const uint2* __restr
     }
     uint32_t* dst = table + (size_t)g * T + key0;
     if ((nslots & 3u) == 0 && ((((size_t)g * T + key0) & 3u) == 0)) {
+        if constexpr (NTS) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            for (uint32_t i = threadIdx.x; i < nslots / 4; i += NT) __builtin_nontemporal_store(reinterpret_cast<u32x4*>(tab)[i], reinterpret_cast<u32x4*>(dst) + i);
+        } else
         for (uint32_t i = threadIdx.x; i < nslots / 4; i += NT) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<uint4*>(tab)[i];
     } else {
         for (uint32_t i = threadIdx.x; i < nslots; i += NT) dst[i] = tab[i];
