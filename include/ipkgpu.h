@@ -873,6 +873,53 @@ uint64_t ipkgpu_db_diff_files_num_ranges(const ipkgpu_ctx* ctx);
 int ipkgpu_db_diff_files_range(const ipkgpu_ctx* ctx, uint64_t i, uint64_t* key_lo, uint64_t* key_hi);
 double ipkgpu_db_diff_files_stat(const ipkgpu_ctx* ctx, int which);
 
+/* ---- the union of databases with disjoint key sets, on the device ------------------------------------------------------------------------
+ * Shards of several ranks (key % P), the files of key-range passes and the batches of an on-disk build are databases with disjoint
+ * key sets.  ipkgpu_db_union makes one ordinary database of n_srcs of them (db_union.hpp, kernels_dbunion.hpp): every accessor,
+ * ipkgpu_db_write, ipkgpu_db_select, ipkgpu_db_diff and ipkgpu_db_place take it.  The sources belong to ctx, each carries filter
+ * values and an order (loaded from a file, or filtered by ipkgpu_db_filter_mif0 / _random), all have positions or none has; they are
+ * only read and stay valid.  The result U:
+ *   keys        ascending;  key_offsets;  a key's entries and positions bit for bit and in their source's order;
+ *   fv32, fv64  bit for bit the source's (nothing is recomputed);
+ *   order       the keys sorted by the filter stage's own sort key: the order-preserving code of the float32 value, then the key
+ *               (filter_sortkey_kernel; dbfile.filter_sort_code);
+ *   head        ipkgpu_db_header_of(U) is NULL.
+ * THE CONDITION under which ipkgpu_db_write(U) equals ipkgpu_db_merge_files of the sources' files byte for byte: every source is itself
+ * in that order -- order[i] of each source ascends by (code of fv32, key), as the filter calls leave it and as a file written from such a
+ * database holds it.  The host's P-way merge hands the records of such sources out by exactly that key.  A source in another order
+ * (a hand-made file) is still united, its own record order is not kept, and the two files then differ.
+ * IPKGPU_ERR_INVALID with a message, before anything is allocated that outlives the call: n_srcs = 0, a null source, a source of
+ * another context, a source without filter values, a mixture of positioned and plain sources (in ipkgpu_db_merge_files' wording),
+ * more than 2^32 - 1 keys in all, and a key present in two sources -- the message names the key and both source indices; it is found
+ * behind the key sort and before any entry moves.  n_srcs = 1 gives a copy.
+ * Device work: (key << 32 | concatenated index) sorted with the loader's radix sort; per sorted position the source (a search over the
+ * n_srcs + 1 prefix values of a table in device memory, n_srcs unbounded), key, filter values, entry count and entry start; a scan of
+ * the counts; the entries copied by ENTRY ranges of 1024 per workgroup (as ipkgpu_db_load's and the selection's copies: a key of one
+ * entry and one of thousands cost alike); the order by the filter stage's sort.  No output position comes from an atomic: the same bits
+ * on every run.
+ * Device memory: everything goes through the context's accounting (ipkgpu_mem_stats, "device_budget_bytes"); the workspace is taken for
+ * the call and given back before it returns.  ipkgpu_db_union_bytes(n, e, S, pos) -- n keys and e entries in all, S sources -- is a true
+ * upper bound of what the call holds on top of its sources, host arithmetic (no GPU); with r, sort and scan as defined for
+ * ipkgpu_db_diff_files_range_bytes above and m(x) = max(x, 256):
+ *       3 r(4 n) + r(8 (n + 1)) + r(8 n) + r(8 e) + pos r(4 e)        the result
+ *     + m(56 (S + 1))                                                 the source table
+ *     + 3 m(8 n) + 2 m(4 n)                                           sort keys unsorted and sorted, entry starts; source indices, counts
+ *     + m(sort(n)) + m(scan(n + 1)) + 256                             rocprim's own, the duplicate index
+ * What does not fit is IPKGPU_ERR_NOMEM and leaves the context usable and the sources intact.
+ * ipkgpu_db_union_time_ms, the context's last union, device ms: 0 = all, 1 = key sort (sort keys to key_offsets), 2 = entry copy,
+ * 3 = order sort.  Option "union_copy_bytes" (ipkgpu_set_option): 0 = the default, 16 -- a lane copies two entries and stores them as
+ * one 16-byte word; 8: one entry per store.  Both forms give the same bits (the 16-byte form was the faster one where measured). */
+int ipkgpu_db_union(ipkgpu_ctx* ctx, const ipkgpu_db* const* srcs, uint32_t n_srcs, ipkgpu_db** out);
+uint64_t ipkgpu_db_union_bytes(uint64_t n_keys, uint64_t n_entries, uint32_t n_srcs, int positioned);
+double ipkgpu_db_union_time_ms(const ipkgpu_ctx* ctx, int which);
+/* ipkgpu_db_merge_files on the device: every path loaded with ipkgpu_db_load (its refusals pass through), the sources united and freed,
+ * the union written under header `h` with the streamed device writer (ipkgpu_db_write) and freed; the out-parameters are
+ * ipkgpu_db_merge_files'.  IPKGPU_ERR_INVALID naming the file: a source whose sequence type, k-mer size or omega bits are not h's, or
+ * whose positions flag is not the first source's.  All sources and the union are resident together: what does not fit is
+ * IPKGPU_ERR_NOMEM -- the call does not fall back to the host merge by itself, its callers decide. */
+int ipkgpu_db_union_files(ipkgpu_ctx* ctx, const ipkgpu_db_header* h, const char* const* paths, uint32_t n_paths, const char* path,
+                          uint64_t* total_kmers, uint64_t* total_entries, uint64_t* bytes_written);
+
 #ifdef __cplusplus
 }
 #endif

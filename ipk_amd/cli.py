@@ -16,6 +16,7 @@ Alignment reduction/extension and RUNNING the ancestral reconstruction are IPK's
   ipk.py diff [-v] [--eps 1e-2 | --exact] A.ipk B.ipk          (the reference's ipkdiff; exit status 1 on a difference)
   ipk.py dump [--limit N] DB.ipk                               (the reference's ipkdump)
   ipk.py place -i DB.ipk -q reads.fasta [-o out.tsv]            (this engine's: the reads' k-mers looked up and summed per branch)
+  ipk.py merge -o OUT.ipk [--on device|host] SHARD.ipk ...     (shard files with disjoint k-mer sets joined into one database file)
 
 --mapping (optional, not in the reference): TSV `ar_node_label <TAB> branch_postorder_id` per ghost node in scoring order;
 replaces the tree-derived plan (synthetic inputs without trees).
@@ -84,9 +85,14 @@ def ipk():
 @click.option("--key-passes", type=int, default=None,
               help="build the database in this many key-range passes (4^j; DNA k = 14..16), one pass' k-mers in device memory at a "
                    "time [auto: one call up to k = 14, 4^(k-14) passes above]")
+@click.option("--union-on-device", is_flag=True,
+              help="key-range builds only: every pass' filtered database stays on the GPU, after the last pass they are united there "
+                   "(ipkgpu_db_union) and written once -- no pass files, no host merge; same file.  What does not fit device memory "
+                   "falls back to pass files and the host merge")
 def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, alpha, categories, k, model, convert_uo,
           no_reduction, reduction_ratio, omega, filter_, mu, ghosts, use_unrooted, merge_branches, ar_dir, ar_only,
-          ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device, key_passes):
+          ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device, key_passes,
+          union_on_device):
     """Computes a database of phylo-k-mers from precomputed ancestral probabilities."""
     import ipk_amd
     from ipk_amd import dbfile, distributed, keyrange, ondisk
@@ -109,6 +115,8 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
             keyrange.plan(sigma, k, key_passes)
         except ValueError as e:
             raise click.UsageError(f"--key-passes: {e}")
+    if union_on_device and not use_passes:
+        raise click.UsageError(f"--union-on-device goes with key-range passes (DNA k > {ipk_amd.max_k(4)}, or --key-passes): other builds write no pass files")
     if on_disk and keep_positions:
         raise click.UsageError("--on-disk does not keep positions (neither does the reference, db_builder.cpp:469): drop --keep-positions or --on-disk")
     if on_disk and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -196,14 +204,18 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     if use_passes:
         n_nodes = num_tree_nodes or n_tree_nodes or len(group_order) + 1
         kr = keyrange.build_db_file(eng, mats, np.array(branches, dtype=np.uint32), k, log_eps, sigma, output, workdir,
-                                    "DNA", tree_index, newick, omega, filter_, n_nodes, key_passes)
+                                    "DNA", tree_index, newick, omega, filter_, n_nodes, key_passes, union_on_device=union_on_device)
         if verbosity:
             # the reference's three stage timers (db_builder.cpp:236,290,336), summed over the passes
             n = kr["passes"]
             click.echo(f"Loaded {len(labels)} node matrices ({arp.sites} sites) in {t_load * 1e3:.0f} ms")
             click.echo(f"Computation time: {kr['score_s'] * 1e3:.0f} ms ({kr['emitted']} scored phylo-k-mers; {n} key-range passes)")
             click.echo(f"Filtering time: {kr['filter_s'] * 1e3:.0f} ms ({n} key-range passes)")
-            click.echo(f"Merge time: {(kr['write_s'] + kr['merge_s']) * 1e3:.0f} ms ({n} pass files written and merged)")
+            if kr["route"] == "device":
+                click.echo(f"Merge time: {(kr['write_s'] + kr['union_s']) * 1e3:.0f} ms ({n} pass databases united on the device, one file written)")
+            else:
+                click.echo(f"Merge time: {(kr['write_s'] + kr['merge_s']) * 1e3:.0f} ms ({n} pass files written and merged"
+                           + ("; --union-on-device did not fit device memory)" if kr["route"] == "fallback" else ")"))
             click.echo(f"Output: {output} ({kr['totals'][0]} k-mers, {kr['totals'][1]} entries)")
         eng.close(); arp.close()
         return
@@ -546,7 +558,8 @@ def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, key_r
 
 
 @ipk.command()
-@click.option("-i", "--input", "db_path", required=True, type=click.Path(exists=True, dir_okay=False), help="database file (of this engine's builds)")
+@click.option("-i", "--input", "db_paths", required=True, multiple=True, type=click.Path(exists=True, dir_okay=False),
+              help="database file (of this engine's builds); repeated: shard files with disjoint k-mer sets, united on the GPU")
 @click.option("-q", "--queries", required=True, type=click.Path(exists=True, dir_okay=False), help="query sequences (FASTA)")
 @click.option("-o", "--output", default=None, help="output TSV [standard output]")
 @click.option("--keep-at-most", type=click.IntRange(1, 64), default=7, show_default=True, help="placements kept per query at most")
@@ -561,7 +574,7 @@ def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, key_r
               help="never hold the file on the GPU: stream it in windows and keep only the k-mers the queries look up (same output)")
 @click.option("--query-batch", type=click.IntRange(1), default=None, help="with --stream-db: queries per pass over the file [all]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, stream_db, query_batch, device):
+def place(db_paths, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, stream_db, query_batch, device):
     """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
     branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
 
@@ -574,9 +587,18 @@ def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous,
     read) and place on it, at --omega's threshold; what `subset` with the same options writes places alike.
 
     --stream-db is for a file that does not fit the GPU's memory: per --query-batch queries the file goes through the GPU in bounded
-    windows and only the k-mers those queries can look up stay (ipkgpu_db_load_wanted).  The TSV is the same."""
+    windows and only the k-mers those queries can look up stay (ipkgpu_db_load_wanted).  The TSV is the same.
+
+    Several -i name a shard set -- ranks' shards, pass files -- whose k-mer sets are disjoint: each file is loaded, the databases are
+    united on the GPU (ipkgpu_db_union) and --mu / --omega select from the union; the TSV is that of the merged file."""
     import ipk_amd
-    _check_selection(db_path, mu, omega)
+    if len(db_paths) > 1 and stream_db:
+        raise click.UsageError("--stream-db takes one -i: a shard set is united on the GPU, which holds every shard")
+    db_path = db_paths[0]
+    if len(db_paths) > 1:
+        _shard_set_head(db_paths)
+    for p in db_paths:
+        _check_selection(p, mu, omega)
     with open(queries) as fh:
         recs = read_fasta(fh.read())
     eng = ipk_amd.Engine(device)
@@ -585,6 +607,13 @@ def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous,
         if stream_db:
             res = eng.place_file(db_path, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands, mu=mu, omega=omega,
                                  query_batch=query_batch)
+        elif len(db_paths) > 1:
+            whole, _ = eng.load_dbs(db_paths)
+            d = whole
+            if mu is not None or omega is not None:
+                d = eng.select_db(whole, mu=mu, omega=omega)
+                whole.free()
+            res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
         else:
             d = eng.load_db(db_path, mu=mu, omega=omega)
             res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
@@ -598,6 +627,56 @@ def place(db_path, queries, output, keep_at_most, keep_factor, expand_ambiguous,
             d.free()
     finally:
         eng.close()
+
+
+# ---- joining shard files ---------------------------------------------------------------------------------------------------------
+
+def _shard_set_head(paths):
+    """The head of a shard set (engine.shard_set_head); a file that disagrees is a usage error that names it."""
+    from ipk_amd import dbfile
+    from ipk_amd.engine import IpkGpuError, shard_set_head
+    try:
+        return shard_set_head([dbfile.file_info(p) for p in paths], list(paths))
+    except IpkGpuError as e:
+        raise click.UsageError(str(e))
+    except ValueError as e:
+        raise click.UsageError(str(e))
+
+
+@ipk.command()
+@click.option("-o", "--output", required=True, help="the merged database file")
+@click.option("--on", "on", type=click.Choice(["device", "host"]), default="device", show_default=True,
+              help="device: the shards are loaded, united on the GPU and written by the device writer; host: the streaming merge on the host (no GPU)")
+@click.option("--device", type=int, default=0, show_default=True, help="GPU index")
+@click.argument("shards", nargs=-1, required=True, type=click.Path(exists=True, dir_okay=False))
+def merge(output, on, device, shards):
+    """Joins database files with disjoint k-mer sets -- the shards of several ranks, the files of key-range passes, the batches of an
+    on-disk build -- into one database file, its records in filter order.
+
+    The shards must agree on sequence type, k, omega and the positions flag.  The tree of the output is that of the first shard
+    that carries one (pass files and ranks' shards carry none).  Both routes write the same bytes for shards that are each in filter
+    order, as every build writes them.  --on device needs every shard and their union in device memory at once; when they do not fit
+    it says so and the host merge takes over."""
+    from ipk_amd import dbfile
+    head = _shard_set_head(shards)
+    args = (head["sequence_type"], head["tree_index"], head["newick"], head["kmer_size"], head["omega"], list(shards))
+    route = on
+    if on == "device":
+        import ipk_amd
+        from ipk_amd.engine import ERR_NOMEM, IpkGpuError
+        eng = ipk_amd.Engine(device)
+        try:
+            totals = dbfile.union_shard_files(eng, output, *args)
+        except IpkGpuError as e:
+            if e.code != ERR_NOMEM:
+                raise
+            click.echo(f"merge: the shards and their union do not fit device memory ({e}); merging on the host", err=True)
+            route = "host"
+        finally:
+            eng.close()
+    if route == "host":
+        totals = dbfile.merge_shard_files(output, *args)
+    click.echo(f"Output: {output} ({totals[0]} k-mers, {totals[1]} entries; merged on the {route})")
 
 
 if __name__ == "__main__":

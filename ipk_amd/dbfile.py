@@ -334,3 +334,23 @@ def merge_shard_files(path, sequence_type, tree_index, newick, kmer_size, omega,
     if rc != 0:
         raise IpkGpuError(rc, L.ipkgpu_db_merge_last_error().decode())
     return int(nk.value), int(ne.value)
+
+
+def union_shard_files(engine, path, sequence_type, tree_index, newick, kmer_size, omega, shard_paths):
+    """ipkgpu_db_union_files: merge_shard_files on the device -- every shard loaded, the databases united (ipkgpu_db_union), the union
+    written by the streamed device writer.  The same file byte for byte for shards that are each in filter order, and the same return
+    value (total k-mers, total entries).  All shards and the union are on the device together: IpkGpuError with code 3
+    (IPKGPU_ERR_NOMEM) when they do not fit -- the caller decides whether merge_shard_files takes over."""
+    L = _lib()
+    if not getattr(L, "_union_files_bound", False):
+        L.ipkgpu_db_union_files.restype = C.c_int
+        L.ipkgpu_db_union_files.argtypes = [C.c_void_p, C.POINTER(_Header), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L._union_files_bound = True
+    h = _header(sequence_type, tree_index, newick, kmer_size, omega)
+    arr = (C.c_char_p * max(len(shard_paths), 1))(*[os.fsencode(p) for p in shard_paths])
+    nk, ne, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = L.ipkgpu_db_union_files(engine._h, C.byref(h), arr, len(shard_paths), os.fsencode(path), C.byref(nk), C.byref(ne), C.byref(nb))
+    if rc != 0:
+        raise engine._err(rc)
+    return int(nk.value), int(ne.value)

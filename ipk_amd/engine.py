@@ -952,7 +952,11 @@ def _select_db(self, db, keep_kmers=None, mu=None, min_log_score=None, omega=Non
     rc = self._lib.ipkgpu_db_select(self._h, db._h, m, C.c_float(t), C.byref(out))
     if rc != 0:
         raise self._err(rc)
-    return _finish_selection(self, out, omega if omega is not None else db.omega)
+    sel = _finish_selection(self, out, omega if omega is not None else db.omega)
+    if sel.header is None and db.header is not None:
+        # a union of files (load_dbs) has no file behind it: its head is the shard set's, kept on the Python side alone
+        sel.header = dict(db.header, total_num_kmers=sel.num_keys, total_num_entries=sel.num_entries)
+    return sel
 
 
 def _select_time_ms(self):
@@ -1397,3 +1401,100 @@ def _concat_placements(parts):
 
 Engine.kmer_set = _kmer_set
 Engine.place_file = _place_file
+
+
+# ---- the union of databases with disjoint key sets (ipkgpu_db_union) ----------------------------------------------------------------
+
+ABI_SYMBOLS += ["ipkgpu_db_union", "ipkgpu_db_union_bytes", "ipkgpu_db_union_time_ms", "ipkgpu_db_union_files"]
+
+UNION_TIMES = ("total_ms", "key_sort_ms", "entry_copy_ms", "order_sort_ms")
+
+
+def _bind_union(L):
+    if getattr(L, "_union_bound", False):
+        return
+    L.ipkgpu_db_union.restype = C.c_int
+    L.ipkgpu_db_union.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_union_bytes.restype = C.c_uint64
+    L.ipkgpu_db_union_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int]
+    L.ipkgpu_db_union_time_ms.restype = C.c_double
+    L.ipkgpu_db_union_time_ms.argtypes = [C.c_void_p, C.c_int]
+    L._union_bound = True
+
+
+def union_bytes(n_keys, n_entries, n_srcs, positioned):
+    """ipkgpu_db_union_bytes: the peak device bytes a union of n_srcs databases with n_keys keys and n_entries entries in all holds on
+    top of its sources -- the result and the workspace (the formula of include/ipkgpu.h; no GPU)."""
+    L = load_library()
+    _bind_union(L)
+    return int(L.ipkgpu_db_union_bytes(int(n_keys), int(n_entries), int(n_srcs), int(bool(positioned))))
+
+
+def _union_dbs(self, dbs):
+    """ipkgpu_db_union: the databases `dbs` of this engine, whose key sets are disjoint and which all carry filter values (loaded, or
+    filtered), as ONE ordinary Db -- keys ascending, every key's entries, positions and filter values bit for bit its source's, the order
+    by (filter value, key).  The sources are only read and stay valid.  `.header` is None."""
+    _bind_keymajor(self._lib)
+    _bind_union(self._lib)
+    dbs = list(dbs)
+    arr = (C.c_void_p * max(len(dbs), 1))(*[d._h for d in dbs])
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_db_union(self._h, arr, len(dbs), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return self._adopt(Db(self._lib, out))
+
+
+def _union_times(self):
+    """Device milliseconds of the engine's last union: all, the key sort (sort keys to key offsets), the entry copy, the order sort."""
+    _bind_union(self._lib)
+    return {k: float(self._lib.ipkgpu_db_union_time_ms(self._h, i)) for i, k in enumerate(UNION_TIMES)}
+
+
+def shard_set_head(infos, names):
+    """The head a set of shard files stands for, from their file_info dicts: sequence type, k, omega and the positions flag must agree
+    (ValueError naming the file that differs); the tree is the first non-empty newick's -- pass files and ranks' shards carry an empty
+    one -- and two different non-empty trees are an error.  Returns header_args' dict plus "positions_loaded"."""
+    if not infos:
+        raise ValueError("no database file given")
+    first = infos[0]
+    tree = None
+    for info, name in zip(infos, names):
+        for field, what in (("sequence_type", "sequence type"), ("kmer_size", "k"), ("positions_loaded", "positions flag")):
+            if info[field] != first[field]:
+                raise ValueError(f"{name}: {what} {info[field]} differs from {names[0]}'s {first[field]}")
+        if np.float32(info["omega"]).view(np.uint32) != np.float32(first["omega"]).view(np.uint32):
+            raise ValueError(f"{name}: omega {info['omega']} differs from {names[0]}'s {first['omega']}")
+        if info["newick"]:
+            if tree is None:
+                tree = (info, name)
+            elif info["newick"] != tree[0]["newick"] or info["tree_index"] != tree[0]["tree_index"]:
+                raise ValueError(f"{name}: its tree differs from {tree[1]}'s")
+    src = tree[0] if tree else first
+    return dict(sequence_type=first["sequence_type"], tree_index=src["tree_index"], newick=src["newick"], kmer_size=first["kmer_size"],
+                omega=first["omega"], positions_loaded=first["positions_loaded"])
+
+
+def _load_dbs(self, paths):
+    """Several database files with disjoint key sets as one Db: each is loaded (load_db), the heads are checked to agree
+    (shard_set_head), the databases are united (union_dbs) and the sources freed.  Returns (Db, head): head is shard_set_head's dict
+    with the union's totals, and is also the Db's `.header`, so select_db(omega=) and place take the union like a loaded file."""
+    paths = [os.fspath(p) for p in paths]
+    srcs = []
+    try:
+        for p in paths:
+            srcs.append(self.load_db(p))
+        head = shard_set_head([d.header for d in srcs], paths)
+        db = self.union_dbs(srcs)
+    finally:
+        for d in srcs:
+            d.free()
+    head.update(total_num_kmers=db.num_keys, total_num_entries=db.num_entries)
+    db.header = head
+    return db, head
+
+
+Engine.union_dbs = _union_dbs
+Engine.union_bytes = staticmethod(union_bytes)
+Engine.union_times = _union_times
+Engine.load_dbs = _load_dbs

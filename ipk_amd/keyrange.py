@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import dbfile
-from .engine import T_KM_WRITE, T_SCORE_MAIN, T_SCORE_REDUCE, T_TOTAL, score_threshold
+from .engine import ERR_NOMEM, IpkGpuError, T_KM_WRITE, T_SCORE_MAIN, T_SCORE_REDUCE, T_TOTAL, score_threshold
 
 KEY_SYMBOLS = (13, 14)            # k - j of a pass: the key spaces of the exact partition's 32768-slot buckets
 MAX_K = 16                        # u32 keys: 2 bits per DNA symbol
@@ -45,10 +45,15 @@ def plan(sigma, k, passes=None):
 
 
 def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, sequence_type, tree_index, newick, omega,
-                  filter_="mif0", total_num_groups=None, passes=None, keep_pass_files=False):
+                  filter_="mif0", total_num_groups=None, passes=None, keep_pass_files=False, union_on_device=False):
     """Scores every pass, writes its filtered shard to workdir/passes/pass<c>.ipk and merges the pass files into `path`.
     mats: [n_mats, sites, sigma] float32 (numpy or CUDA tensor; uploaded once).  Returns a dict with the totals, `emitted`,
-    the number of passes, stage times summed over the passes (seconds) and per-pass device timings (ms)."""
+    the number of passes, stage times summed over the passes (seconds) and per-pass device timings (ms).
+    union_on_device: every pass' filtered database stays on the device instead; after the last pass they are united there
+    (Engine.union_dbs), written once under the real header and freed -- the same file byte for byte, no pass files, no host merge.
+    On the first IPKGPU_ERR_NOMEM anywhere in that mode the held databases are written as pass files and freed, the failed step is
+    repeated once, and the build goes on in the file mode.  "route" says which way the file came about: "files" (the default),
+    "device" or "fallback"; "union_s" is the time in the union and its write."""
     import torch
 
     steps = plan(sigma, k, passes)
@@ -60,16 +65,78 @@ def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, seq
     thr = score_threshold(omega, sigma, k)
     n_nodes = total_num_groups or len(np.unique(mat_group)) + 1
     out = {"passes": len(steps), "lead": steps[0][0], "emitted": 0, "score_s": 0.0, "filter_s": 0.0, "write_s": 0.0,
-           "merge_s": 0.0, "per_pass": []}
+           "merge_s": 0.0, "union_s": 0.0, "route": "device" if union_on_device else "files", "per_pass": []}
     paths = []
-    for lead, cls, base, span in steps:
+    held = []                         # union_on_device: (pass file's path, filtered database) of the passes so far
+
+    def spill_held():
+        # the device route has run out of memory: what it holds becomes pass files, and the build is the file mode's from here on
         t0 = time.time()
-        parts = engine.score_groups_keyrange(mats, mat_group, k, log_eps, lead, cls)
-        db = engine.db_from_parts(parts, sigma, k)
-        t1 = time.time()
+        for file, d in held:
+            dbfile.write_db_device(engine, d, file, sequence_type, [], "", k, omega)
+            d.free()
+        del held[:]
+        out["write_s"] += time.time() - t0
+        out["route"] = "fallback"
+
+    def on_device(step, again=True):
+        # one step of the device route; IPKGPU_ERR_NOMEM: fall back, then the step once more (another failure stands) -- but for the
+        # union itself, which the host merge of the pass files replaces
+        try:
+            return step()
+        except IpkGpuError as e:
+            if e.code != ERR_NOMEM or out["route"] != "device":
+                raise
+        spill_held()
+        return step() if again else None
+
+    def filter_db(d):
+        t0 = time.time()
+        if filter_ == "mif0":
+            d.filter_mif0(engine, n_nodes, thr)
+        elif filter_ == "random":
+            d.filter_random(engine)
+        else:
+            raise ValueError(f"unknown filter {filter_!r} (mif0, random)")
+        return time.time() - t0
+
+    for lead, cls, base, span in steps:
         file = os.path.join(pdir, f"pass{cls}.ipk")
-        filter_s, write_s = dbfile.filter_and_write_device(engine, db, file, filter_, sequence_type, [], "", k, omega, n_nodes, thr)
         paths.append(file)
+        if out["route"] == "device":
+            state = {}
+
+            def score_pass():
+                for key in ("db", "parts"):
+                    if state.get(key) is not None:
+                        state.pop(key).free()
+                state["parts"] = engine.score_groups_keyrange(mats, mat_group, k, log_eps, lead, cls)
+                state["db"] = engine.db_from_parts(state["parts"], sigma, k)
+                state["t1"] = time.time()
+                return filter_db(state["db"])
+            t0 = time.time()
+            try:
+                filter_s = on_device(score_pass)
+            except BaseException:
+                for key in ("db", "parts"):
+                    if state.get(key) is not None:
+                        state[key].free()
+                for _, d in held:
+                    d.free()
+                raise
+            parts, db, t1, write_s = state["parts"], state["db"], state["t1"], 0.0
+            if out["route"] == "device":
+                held.append((file, db))
+            else:
+                t2 = time.time()
+                dbfile.write_db_device(engine, db, file, sequence_type, [], "", k, omega)
+                write_s = time.time() - t2
+        else:
+            t0 = time.time()
+            parts = engine.score_groups_keyrange(mats, mat_group, k, log_eps, lead, cls)
+            db = engine.db_from_parts(parts, sigma, k)
+            t1 = time.time()
+            filter_s, write_s = dbfile.filter_and_write_device(engine, db, file, filter_, sequence_type, [], "", k, omega, n_nodes, thr)
         out["emitted"] += parts.emitted
         out["score_s"] += t1 - t0
         out["filter_s"] += filter_s
@@ -78,11 +145,35 @@ def build_db_file(engine, mats, mat_group, k, log_eps, sigma, path, workdir, seq
                                 "emitted": parts.emitted, "call_ms": parts.time_ms(T_TOTAL), "score_ms": parts.time_ms(T_SCORE_MAIN),
                                 "reduce_ms": parts.time_ms(T_SCORE_REDUCE), "writer_ms": parts.time_ms(T_KM_WRITE),
                                 "keys_ms": db.time_ms(), "shard_file_s": write_s})
-        db.free()
+        if not (held and held[-1][1] is db):
+            db.free()
         parts.free()
-    t0 = time.time()
-    out["totals"] = dbfile.merge_shard_files(path, sequence_type, tree_index, newick, k, omega, paths)
-    out["merge_s"] = time.time() - t0
+    if out["route"] == "device":
+        def union_and_write():
+            u = engine.union_dbs([d for _, d in held])
+            try:
+                dbfile.write_db_device(engine, u, path, sequence_type, tree_index, newick, k, omega)
+                return u.num_keys, u.num_entries
+            finally:
+                u.free()
+        t0 = time.time()
+        try:
+            totals = on_device(union_and_write, again=False)
+        except BaseException:
+            for _, d in held:
+                d.free()
+            raise
+        if out["route"] == "device":
+            out["totals"] = totals
+            out["union_s"] = time.time() - t0
+            for _, d in held:
+                d.free()
+            del held[:]
+            paths = []
+    if out["route"] != "device":
+        t0 = time.time()
+        out["totals"] = dbfile.merge_shard_files(path, sequence_type, tree_index, newick, k, omega, paths)
+        out["merge_s"] = time.time() - t0
     if not keep_pass_files:
         for p in paths:
             os.remove(p)
