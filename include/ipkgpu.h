@@ -891,7 +891,7 @@ double ipkgpu_db_diff_files_stat(const ipkgpu_ctx* ctx, int which);
  * IPKGPU_ERR_INVALID with a message, before anything is allocated that outlives the call: n_srcs = 0, a null source, a source of
  * another context, a source without filter values, a mixture of positioned and plain sources (in ipkgpu_db_merge_files' wording),
  * more than 2^32 - 1 keys in all, and a key present in two sources -- the message names the key and both source indices; it is found
- * behind the key sort and before any entry moves.  n_srcs = 1 gives a copy.
+ * behind the key sort and before any entry moves (ipkgpu_db_join below takes such sources).  n_srcs = 1 gives a copy.
  * Device work: (key << 32 | concatenated index) sorted with the loader's radix sort; per sorted position the source (a search over the
  * n_srcs + 1 prefix values of a table in device memory, n_srcs unbounded), key, filter values, entry count and entry start; a scan of
  * the counts; the entries copied by ENTRY ranges of 1024 per workgroup (as ipkgpu_db_load's and the selection's copies: a key of one
@@ -919,6 +919,62 @@ double ipkgpu_db_union_time_ms(const ipkgpu_ctx* ctx, int which);
  * IPKGPU_ERR_NOMEM -- the call does not fall back to the host merge by itself, its callers decide. */
 int ipkgpu_db_union_files(ipkgpu_ctx* ctx, const ipkgpu_db_header* h, const char* const* paths, uint32_t n_paths, const char* path,
                           uint64_t* total_kmers, uint64_t* total_entries, uint64_t* bytes_written);
+
+/* ---- the join of databases that share k-mers, on the device --------------------------------------------------------------------------------
+ * Databases built over DIFFERENT BRANCH GROUPS of one tree (branch shards: `ipk.py build --group-range`, one job of an array each) hold
+ * the same k-mers with different branches.  ipkgpu_db_union refuses them; ipkgpu_db_join makes one ordinary database of n_srcs of them
+ * (db_join.hpp, kernels_dbjoin.hpp) by the rule with which the reference merges pieces of groups, `put` (branch_group.cpp:88-101,
+ * db_builder.cpp:392-458).  The sources belong to ctx and all have positions or none has; they need NO filter values and no order (a
+ * fresh ipkgpu_db_from_parts / ipkgpu_merge_parts result serves as a loaded file does); within one source a key's entries have distinct
+ * branches, as in every database the engine makes or loads for placement.  They are only read and stay valid.  The result J:
+ *   keys        the set union of the sources' keys, ascending;  key_offsets goes with it;
+ *   entries     of key K: (1) the entries of K in source 0, 1, ..., S - 1, each in its source's order, concatenated; (2) of a branch
+ *               that occurs more than once ONE entry stays, at the place of its first occurrence; (3) its score: walking the
+ *               occurrences in order, a later one replaces the kept score only if it is strictly greater (`>` on the floats: equal
+ *               scores, -0.0 against +0.0 and a NaN keep the earlier one); (4) its window position is the kept score's;
+ *               a key without entries in every source that holds it stays a record without entries;
+ *   fv32, fv64, order, head     none (ipkgpu_db_header_of(J) is NULL): the caller runs ipkgpu_db_filter_mif0 or _random on J as on any
+ *               merged database; then ipkgpu_db_write, _select, _diff, _place and _union take it.
+ * Disjoint key sets are a special case: keys, offsets, entries and positions are ipkgpu_db_union's.
+ * WHY THE JOIN OF GROUP RANGES IS THE WHOLE BUILD: a build leaves a key's entries in group order; ipkgpu_db_filter_mif0 adds the
+ * entries' terms in entry order; the random filter draws per k-mer code.  Shards of CONTIGUOUS ranges of the group order, joined in range
+ * order and filtered with the whole tree's N, therefore give the one-call build's file byte for byte (another order of the sources gives
+ * the same keys and counts and another entry order).
+ * IPKGPU_ERR_INVALID with a message, before anything is allocated that outlives the call: n_srcs = 0, a null source, a source of
+ * another context, a mixture of positioned and plain sources (ipkgpu_db_union's wording), more than 2^32 - 1 keys in all sources (the
+ * sort's low word is the concatenated key index; the result holds no more), more entries than one launch covers (2^39 - 256).
+ * Device work.  A RUN is one source's record of one key.  (key << 32 | concatenated key index) sorted with the loader's radix sort:
+ * the runs of a key then stand side by side in source order.  Segment heads give J's keys; a scan of the head flags numbers them, a
+ * scan of the runs' counts gives every run's -- and at the heads every key's -- offset in the CONCATENATED layout.  The entries are
+ * copied by ENTRY ranges of 1024 per workgroup with the union's copy kernel, its "keys" being the runs: a lane searches (sorted
+ * position, source run).  Whether duplicates can exist is decided from the sources: some key must have two runs, and a table of
+ * 2^18 slots (branch mod 2^18), filled with the smallest and the largest source that holds a branch of the slot, must show a slot
+ * with two sources (never wrong towards "none"; branch ids below 2^18 make it exact).  If they cannot, the copy goes straight into J
+ * (route 0).  Else (route 1) it goes into a workspace and every joined list is resolved where it lies: up to 64 entries by one wavefront,
+ * lane against lane; up to 4096 by a workgroup that sorts (branch, index) in LDS and walks each run of equal branches; longer ones by a
+ * radix sort of ((key index << 32 | branch), entry index) pairs over the layout and the same walk.  The kept flags are scanned and the
+ * kept entries, positions and key offsets compacted into J.  No output position comes from an atomic: the same bits on every run.
+ * Option "join_route" (ipkgpu_set_option): 0 = decide as above; 1 = always resolve; 2 = decide, and IPKGPU_ERR_INVALID if a duplicate
+ * exists -- the message names a key, a branch and the two sources that hold it -- for callers who expect branch-disjoint shards.
+ * Routes 0 and 1 give the same bits.
+ * Device memory: everything goes through the context's accounting (ipkgpu_mem_stats, "device_budget_bytes"); the workspace is taken for
+ * the call and given back before it returns.  ipkgpu_db_join_bytes(n, e, S, pos) -- n keys and e entries IN ALL SOURCES, S sources -- is
+ * a true upper bound of what the call holds on top of its sources, host arithmetic (no GPU); r, sort, scan and m as for
+ * ipkgpu_db_union_bytes:
+ *       r(4 max(n, 1)) + r(8 (n + 1)) + r(8 max(e, 1)) + pos r(4 max(e, 1))     the result (it has no filter arrays)
+ *     + m(56 (S + 1)) + m(8 (S + 1))                                            the source table, the sources' entry prefix
+ *     + 3 m(8 n) + 3 m(4 n) + 2 m(8 (n + 1))          sort keys unsorted and sorted, entry starts; sources, counts, head flags; the two scans
+ *     + m(sort(n)) + m(scan(max(n, e) + 1)) + 256 + 2 m(4 * 2^18)               rocprim's own, the counters, the branch table
+ *     + m(8 (n + 1)) + m(8 e) + pos m(4 e) + m(4 e) + m(8 (e + 1)) + m(4 (e / 65 + 1))
+ *                                       route 1: concatenated offsets, entries, positions; kept flags and their scan; the long lists
+ *     + (e > 4096 ?  4 m(8 e) + m(17 e + 32768)  :  0)                          the sorted pass, taken only for a list beyond 4096
+ * What does not fit is IPKGPU_ERR_NOMEM and leaves the context usable and the sources intact.
+ * ipkgpu_db_join_stat, the context's last join: 0 = device ms in all, 1 = key stage (sort keys to the offsets), 2 = entry copy,
+ * 3 = duplicate stage (resolution, scan and compaction), 4 = J-keys found in more than one source, 5 = entries dropped as duplicates,
+ * 6 = route taken (0 concatenation only, 1 duplicates resolved). */
+int ipkgpu_db_join(ipkgpu_ctx* ctx, const ipkgpu_db* const* srcs, uint32_t n_srcs, ipkgpu_db** out);
+uint64_t ipkgpu_db_join_bytes(uint64_t keys_in_all, uint64_t entries_in_all, uint32_t n_srcs, int positioned);
+double ipkgpu_db_join_stat(const ipkgpu_ctx* ctx, int which);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,8 @@ Alignment reduction/extension and RUNNING the ancestral reconstruction are IPK's
   ipk.py dump [--limit N] DB.ipk                               (the reference's ipkdump)
   ipk.py place -i DB.ipk -q reads.fasta [-o out.tsv]            (this engine's: the reads' k-mers looked up and summed per branch)
   ipk.py merge -o OUT.ipk [--on device|host] SHARD.ipk ...     (shard files with disjoint k-mer sets joined into one database file)
+  ipk.py build ... --group-range LO:HI -o SHARD.ipk            (a branch shard: only the branch groups LO <= i < HI are scored)
+  ipk.py merge --shared-keys -o OUT.ipk SHARD.ipk ...          (branch shards, whose k-mer sets overlap, joined and filtered anew)
 
 --mapping (optional, not in the reference): TSV `ar_node_label <TAB> branch_postorder_id` per ghost node in scoring order;
 replaces the tree-derived plan (synthetic inputs without trees).
@@ -89,10 +91,14 @@ def ipk():
               help="key-range builds only: every pass' filtered database stays on the GPU, after the last pass they are united there "
                    "(ipkgpu_db_union) and written once -- no pass files, no host merge; same file.  What does not fit device memory "
                    "falls back to pass files and the host merge")
+@click.option("--group-range", default=None, metavar="LO:HI",
+              help="score only the branch groups at positions LO <= i < HI of the first-seen group order and write them as an ordinary "
+                   "database file, a branch shard (MIF0's N stays the whole tree's); `merge --shared-keys` joins the shards of all "
+                   "ranges, in range order, into the file of the whole build.  One GPU, no --on-disk, no key-range passes")
 def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, alpha, categories, k, model, convert_uo,
           no_reduction, reduction_ratio, omega, filter_, mu, ghosts, use_unrooted, merge_branches, ar_dir, ar_only,
           ar_config, keep_positions, uncompressed, threads, output, on_disk, mapping, num_tree_nodes, device, key_passes,
-          union_on_device):
+          union_on_device, group_range):
     """Computes a database of phylo-k-mers from precomputed ancestral probabilities."""
     import ipk_amd
     from ipk_amd import dbfile, distributed, keyrange, ondisk
@@ -123,6 +129,14 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
         raise click.UsageError("--on-disk runs on ONE GPU: the batches inside a rank's shard would need a slot mapping of their own (not built)")
     if on_disk and use_passes:
         raise click.UsageError(f"--on-disk is not combined with key-range passes (k = {k} / --key-passes): a pass already bounds device memory")
+    if group_range is not None:
+        group_range = _parse_group_range(group_range)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise click.UsageError("--group-range runs on ONE GPU: give every process its own range and join the files with `merge --shared-keys`")
+        if on_disk:
+            raise click.UsageError("--group-range is not combined with --on-disk")
+        if use_passes:
+            raise click.UsageError(f"--group-range is not combined with key-range passes (k = {k} / --key-passes)")
     os.makedirs(workdir, exist_ok=True)
     output = output or os.path.join(workdir, "DB.ipk")
 
@@ -188,6 +202,10 @@ def build(ar, refalign, reftree, states, verbosity, workdir, write_reduction, al
     all_branches = list(branches)
     group_order = list(dict.fromkeys(all_branches))                        # first-seen order (db_builder.cpp:524-553)
     g0, g1 = distributed.shard_range(len(group_order), world, rank)
+    if group_range is not None:
+        g0, g1 = group_range
+        if g1 > len(group_order):
+            raise click.UsageError(f"--group-range {g0}:{g1}: there are {len(group_order)} branch groups")
     mine = set(group_order[g0:g1])
     sel = [i for i, b in enumerate(all_branches) if b in mine]
     labels, branches = [labels[i] for i in sel], [all_branches[i] for i in sel]
@@ -410,6 +428,17 @@ def diff(verbose, eps, exact, max_records, stream, budget_mib, device, a, b):
     sys.exit(0 if all_ok else 1)
 
 
+def _parse_group_range(text):
+    """LO:HI -> (lo, hi): decimal integers, 0 <= LO < HI."""
+    try:
+        lo, hi = (int(x) for x in text.split(":"))
+    except ValueError:
+        raise click.UsageError(f"--group-range takes LO:HI, two integers, not '{text}'")
+    if not 0 <= lo < hi:
+        raise click.UsageError("--group-range needs 0 <= LO < HI")
+    return lo, hi
+
+
 def _parse_key_range(text):
     """LO:HI -> (lo, hi): integers (0x.. allowed), 0 <= LO <= HI <= 2^32."""
     try:
@@ -573,8 +602,11 @@ def subset(db_path, output, mu, omega, queries, expand_ambiguous, strands, key_r
 @click.option("--stream-db", is_flag=True, default=False,
               help="never hold the file on the GPU: stream it in windows and keep only the k-mers the queries look up (same output)")
 @click.option("--query-batch", type=click.IntRange(1), default=None, help="with --stream-db: queries per pass over the file [all]")
+@click.option("--shared-keys", is_flag=True, default=False,
+              help="several -i are branch shards whose k-mer sets may overlap: joined on the GPU in the order given and filtered with MIF0")
+@click.option("--num-tree-nodes", type=int, default=0, help="with --shared-keys: MIF0's N [the node count of the first shard's tree index]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
-def place(db_paths, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, stream_db, query_batch, device):
+def place(db_paths, queries, output, keep_at_most, keep_factor, expand_ambiguous, strands, mu, omega, stream_db, query_batch, shared_keys, num_tree_nodes, device):
     """Places query sequences on a database: the database is loaded onto the GPU, every read's k-mers are looked up there and each
     branch's scores summed (ipkgpu_db_place; the definition is in include/ipkgpu.h).
 
@@ -590,13 +622,20 @@ def place(db_paths, queries, output, keep_at_most, keep_factor, expand_ambiguous
     windows and only the k-mers those queries can look up stay (ipkgpu_db_load_wanted).  The TSV is the same.
 
     Several -i name a shard set -- ranks' shards, pass files -- whose k-mer sets are disjoint: each file is loaded, the databases are
-    united on the GPU (ipkgpu_db_union) and --mu / --omega select from the union; the TSV is that of the merged file."""
+    united on the GPU (ipkgpu_db_union) and --mu / --omega select from the union; the TSV is that of the merged file.
+
+    --shared-keys: the -i files are branch shards (`build --group-range`), whose k-mer sets may overlap: they are joined in the order
+    given (ipkgpu_db_join), the join is filtered with MIF0 and --mu / --omega select from it; the TSV is that of the whole build's file."""
     import ipk_amd
+    if shared_keys and stream_db:
+        raise click.UsageError("--shared-keys does not go with --stream-db: the join holds every shard on the GPU")
     if len(db_paths) > 1 and stream_db:
         raise click.UsageError("--stream-db takes one -i: a shard set is united on the GPU, which holds every shard")
     db_path = db_paths[0]
-    if len(db_paths) > 1:
-        _shard_set_head(db_paths)
+    head = None
+    if len(db_paths) > 1 or shared_keys:
+        head = _shard_set_head(db_paths)
+    n_nodes = _join_num_nodes(head, num_tree_nodes) if shared_keys else 0
     for p in db_paths:
         _check_selection(p, mu, omega)
     with open(queries) as fh:
@@ -607,6 +646,23 @@ def place(db_paths, queries, output, keep_at_most, keep_factor, expand_ambiguous
         if stream_db:
             res = eng.place_file(db_path, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands, mu=mu, omega=omega,
                                  query_batch=query_batch)
+        elif shared_keys:
+            srcs = []
+            try:
+                for p in db_paths:
+                    srcs.append(eng.load_db(p))
+                whole = eng.join_dbs(srcs)
+            finally:
+                for s in srcs:
+                    s.free()
+            sigma = {"DNA": 4, "AA": 20}[head["sequence_type"]]
+            whole.filter_mif0(eng, n_nodes, ipk_amd.score_threshold(head["omega"], sigma, head["kmer_size"]))
+            whole.header = dict(head, total_num_kmers=whole.num_keys, total_num_entries=whole.num_entries)
+            d = whole
+            if mu is not None or omega is not None:
+                d = eng.select_db(whole, mu=mu, omega=omega)
+                whole.free()
+            res = eng.place(d, [s for _, s in recs], keep_at_most=keep_at_most, ambiguity=expand_ambiguous, strands=strands)
         elif len(db_paths) > 1:
             whole, _ = eng.load_dbs(db_paths)
             d = whole
@@ -643,22 +699,62 @@ def _shard_set_head(paths):
         raise click.UsageError(str(e))
 
 
+def _join_num_nodes(head, num_tree_nodes):
+    """MIF0's N of a join: --num-tree-nodes, else the node count of the shard set's tree index; neither is a usage error."""
+    if num_tree_nodes < 0:
+        raise click.UsageError("--num-tree-nodes must be positive")
+    n = num_tree_nodes or len(head["tree_index"])
+    if not n:
+        raise click.UsageError("--shared-keys: MIF0 needs the tree's node count and the shards carry no tree index: give --num-tree-nodes")
+    return n
+
+
 @ipk.command()
 @click.option("-o", "--output", required=True, help="the merged database file")
 @click.option("--on", "on", type=click.Choice(["device", "host"]), default="device", show_default=True,
               help="device: the shards are loaded, united on the GPU and written by the device writer; host: the streaming merge on the host (no GPU)")
+@click.option("--shared-keys", is_flag=True, default=False,
+              help="the files' k-mer sets may overlap (branch shards of `build --group-range`): a shared k-mer's entries are joined in the "
+                   "order of the files, one entry per branch with `put`'s maximum, and the join is filtered anew; --on device only")
+@click.option("--filter", "filter_", type=click.Choice(["mif0", "random"]), default="mif0", show_default=True, help="with --shared-keys: the filter of the output")
+@click.option("--num-tree-nodes", type=int, default=0, help="with --shared-keys: MIF0's N [the node count of the first shard's tree index]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
 @click.argument("shards", nargs=-1, required=True, type=click.Path(exists=True, dir_okay=False))
-def merge(output, on, device, shards):
+def merge(output, on, shared_keys, filter_, num_tree_nodes, device, shards):
     """Joins database files with disjoint k-mer sets -- the shards of several ranks, the files of key-range passes, the batches of an
     on-disk build -- into one database file, its records in filter order.
 
     The shards must agree on sequence type, k, omega and the positions flag.  The tree of the output is that of the first shard
     that carries one (pass files and ranks' shards carry none).  Both routes write the same bytes for shards that are each in filter
     order, as every build writes them.  --on device needs every shard and their union in device memory at once; when they do not fit
-    it says so and the host merge takes over."""
+    it says so and the host merge takes over.
+
+    --shared-keys joins files whose k-mer sets may overlap, in the order given: branch shards, built over different branch groups of
+    one tree (`build --group-range`).  The shards of contiguous group ranges, given in range order and filtered as the build was,
+    give the whole build's file byte for byte.  The join needs every shard and the result in device memory; there is no host route."""
     from ipk_amd import dbfile
     head = _shard_set_head(shards)
+    if shared_keys:
+        if on != "device":
+            raise click.UsageError("--shared-keys goes with --on device only: the host merge cannot join the entries of a shared k-mer")
+        n_nodes = _join_num_nodes(head, num_tree_nodes) if filter_ == "mif0" else 0
+        import ipk_amd
+        from ipk_amd.engine import ERR_NOMEM, IpkGpuError
+        eng = ipk_amd.Engine(device)
+        try:
+            nk, ne, dropped = dbfile.join_shard_files(eng, output, head["sequence_type"], head["tree_index"], head["newick"], head["kmer_size"],
+                                                      head["omega"], list(shards), filter_, n_nodes)
+        except IpkGpuError as e:
+            if e.code != ERR_NOMEM:
+                raise
+            click.echo(f"merge: the shards and their join do not fit device memory ({e}); there is no host route for shared k-mers", err=True)
+            sys.exit(1)
+        finally:
+            eng.close()
+        click.echo(f"Output: {output} ({nk} k-mers, {ne} entries; merged on the device; {dropped} entries joined by put)")
+        return
+    if num_tree_nodes or filter_ != "mif0":
+        raise click.UsageError("--filter and --num-tree-nodes go with --shared-keys: a merge of disjoint k-mer sets keeps the shards' filter values")
     args = (head["sequence_type"], head["tree_index"], head["newick"], head["kmer_size"], head["omega"], list(shards))
     route = on
     if on == "device":

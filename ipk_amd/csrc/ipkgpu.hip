@@ -45,6 +45,7 @@
 #include "kernels_dbselect.hpp"
 #include "kernels_dbdiff.hpp"
 #include "kernels_dbunion.hpp"
+#include "kernels_dbjoin.hpp"
 #include "kernels_place.hpp"
 #include "kernels_kmerset.hpp"
 #include "kernels_dbstream.hpp"
@@ -187,6 +188,8 @@ struct ipkgpu_ctx {
     double t_select_ms = 0;              // device time of the last ipkgpu_db_select (ipkgpu_db_select_time_ms)
     int64_t opt_union_copy = 0;          // "union_copy_bytes": bytes a lane stores in the union's entry copy (0 = the default, 16: the pair form; 8: one entry per store)
     double t_union[4] = {0, 0, 0, 0};    // last ipkgpu_db_union, ms: all, key sort, entry copy, order sort (ipkgpu_db_union_time_ms)
+    int64_t opt_join_route = 0;          // "join_route": 0 = the join decides whether duplicates can exist, 1 = it always resolves them, 2 = it refuses them
+    double join_stat[7] = {0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_join (ipkgpu_db_join_stat)
     // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
     // place_amb: the per-window tables of ambiguous windows (ipkgpu_db_place_opts)
     DevBuf place_seq, place_off, place_out, place_tables, place_small, place_amb;
@@ -564,6 +567,11 @@ int ipkgpu_set_option(ipkgpu_ctx* ctx, const char* name, int64_t value)
     if (!strcmp(name, "union_copy_bytes")) {
         if (value != 0 && value != 8 && value != 16) return fail(ctx, IPKGPU_ERR_INVALID, "union_copy_bytes is 0 (the default), 8 or 16");
         ctx->opt_union_copy = value;
+        return IPKGPU_OK;
+    }
+    if (!strcmp(name, "join_route")) {
+        if (value < 0 || value > 2) return fail(ctx, IPKGPU_ERR_INVALID, "join_route is 0 (decide), 1 (always resolve duplicates) or 2 (refuse duplicates)");
+        ctx->opt_join_route = value;
         return IPKGPU_OK;
     }
     if (!strcmp(name, "place_batch_queries")) {
@@ -3461,4 +3469,5 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 #include "db_stream.hpp"
 #include "db_diff_files.hpp"
 #include "db_union.hpp"
+#include "db_join.hpp"
 #include "comm_rccl.hpp"

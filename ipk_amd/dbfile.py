@@ -354,3 +354,28 @@ def union_shard_files(engine, path, sequence_type, tree_index, newick, kmer_size
     if rc != 0:
         raise engine._err(rc)
     return int(nk.value), int(ne.value)
+
+
+def join_shard_files(engine, output, sequence_type, tree_index, newick, k, omega, paths, filter_, n_nodes):
+    """Database files whose k-mer sets may overlap (branch shards: builds over different branch groups of one tree) joined into one
+    file: every shard loaded, the databases joined in the order given (Engine.join_dbs: `put`'s maximum per branch), the sources freed,
+    the join filtered anew (filter_and_write_device's stage; n_nodes = MIF0's N of the WHOLE tree, the threshold score_threshold of
+    the head's omega and k) and written by the streamed device writer.  Returns (k-mers, entries, entries dropped as duplicates).
+    All shards and the join are on the device together: IpkGpuError with code 3 (IPKGPU_ERR_NOMEM) when they do not fit -- there
+    is no host route for shared keys."""
+    from .engine import score_threshold
+    sigma = {"DNA": 4, "AA": 20}[sequence_type]
+    srcs = []
+    try:
+        for p in paths:
+            srcs.append(engine.load_db(os.fspath(p)))
+        db = engine.join_dbs(srcs)
+    finally:
+        for d in srcs:
+            d.free()
+    try:
+        dropped = int(engine.join_stats()["entries_dropped"])
+        filter_and_write_device(engine, db, output, filter_, sequence_type, tree_index, newick, k, omega, n_nodes, score_threshold(omega, sigma, k))
+        return db.num_keys, db.num_entries, dropped
+    finally:
+        db.free()

@@ -1498,3 +1498,59 @@ Engine.union_dbs = _union_dbs
 Engine.union_bytes = staticmethod(union_bytes)
 Engine.union_times = _union_times
 Engine.load_dbs = _load_dbs
+
+
+# ---- the join of databases that share k-mers (ipkgpu_db_join) -----------------------------------------------------------------------
+
+ABI_SYMBOLS += ["ipkgpu_db_join", "ipkgpu_db_join_bytes", "ipkgpu_db_join_stat"]
+
+JOIN_STATS = ("total_ms", "key_ms", "entry_copy_ms", "duplicate_ms", "shared_keys", "entries_dropped", "route")
+
+
+def _bind_join(L):
+    if getattr(L, "_join_bound", False):
+        return
+    L.ipkgpu_db_join.restype = C.c_int
+    L.ipkgpu_db_join.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ipkgpu_db_join_bytes.restype = C.c_uint64
+    L.ipkgpu_db_join_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int]
+    L.ipkgpu_db_join_stat.restype = C.c_double
+    L.ipkgpu_db_join_stat.argtypes = [C.c_void_p, C.c_int]
+    L._join_bound = True
+
+
+def join_bytes(keys_in_all, entries_in_all, n_srcs, positioned):
+    """ipkgpu_db_join_bytes: an upper bound of the device bytes a join of n_srcs databases with keys_in_all keys and entries_in_all
+    entries in all (summed over the sources) holds on top of its sources (the formula of include/ipkgpu.h; no GPU)."""
+    L = load_library()
+    _bind_join(L)
+    return int(L.ipkgpu_db_join_bytes(int(keys_in_all), int(entries_in_all), int(n_srcs), int(bool(positioned))))
+
+
+def _join_dbs(self, dbs):
+    """ipkgpu_db_join: the databases `dbs` of this engine, whose key sets may overlap, as ONE Db -- the set union of the keys,
+    ascending; a key's entries are its sources' lists concatenated in the order of `dbs`, a branch that occurs again kept once at its
+    first place with the reference's `put` maximum (a later score replaces only if strictly greater; its position goes with it).
+    The sources need no filter values and stay valid.  The result has no filter values, no order and no header: filter it
+    (Db.filter_mif0 / filter_random) before it is written or consumed."""
+    _bind_keymajor(self._lib)
+    _bind_join(self._lib)
+    dbs = list(dbs)
+    arr = (C.c_void_p * max(len(dbs), 1))(*[d._h for d in dbs])
+    out = C.c_void_p()
+    rc = self._lib.ipkgpu_db_join(self._h, arr, len(dbs), C.byref(out))
+    if rc != 0:
+        raise self._err(rc)
+    return self._adopt(Db(self._lib, out))
+
+
+def _join_stats(self):
+    """The engine's last join: device milliseconds in all, in the key stage, the entry copy and the duplicate stage; the keys found in
+    more than one source, the entries dropped as duplicates, the route taken (0 concatenation only, 1 duplicates resolved)."""
+    _bind_join(self._lib)
+    return {k: float(self._lib.ipkgpu_db_join_stat(self._h, i)) for i, k in enumerate(JOIN_STATS)}
+
+
+Engine.join_dbs = _join_dbs
+Engine.join_bytes = staticmethod(join_bytes)
+Engine.join_stats = _join_stats
