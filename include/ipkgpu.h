@@ -117,7 +117,7 @@ int64_t ipkgpu_debug_exec_violations(ipkgpu_ctx* ctx);
  * pieces of the on-disk build; results of calls without such a window do not change);
  * "device_budget_bytes" (ipkgpu_mem_stats below; 0 = none); "db_load_chunk_bytes" (bytes of each of the two pinned buffers a file passes
  * through in ipkgpu_db_load; 0 = the default, 64 MiB, also the most); "db_load_window_bytes" (bytes of the device window of
- * ipkgpu_db_load_wanted and ipkgpu_db_load_key_range; 0 = the default, 256 MiB -- in ipkgpu_db_diff_files a sixteenth of what the budget leaves); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
+ * ipkgpu_db_load_wanted and ipkgpu_db_load_key_range; 0 = the default, 256 MiB -- in ipkgpu_db_diff_files and ipkgpu_db_join_files a sixteenth of what the budget leaves); "place_batch_queries" (queries per batch of ipkgpu_db_place; 0 = automatic);
  * "place_lds_branches" (0..4096: the branch count up to which ipkgpu_db_place keeps a query's sums in LDS; 0 = 4096; tests lower it to reach
  * the global tables with small inputs); "release_workspaces" (any value: the context's workspaces and cached result
  * blocks go back to the device now -- between the stages of the on-disk build; later calls allocate theirs again).
@@ -975,6 +975,72 @@ int ipkgpu_db_union_files(ipkgpu_ctx* ctx, const ipkgpu_db_header* h, const char
 int ipkgpu_db_join(ipkgpu_ctx* ctx, const ipkgpu_db* const* srcs, uint32_t n_srcs, ipkgpu_db** out);
 uint64_t ipkgpu_db_join_bytes(uint64_t keys_in_all, uint64_t entries_in_all, uint32_t n_srcs, int positioned);
 double ipkgpu_db_join_stat(const ipkgpu_ctx* ctx, int which);
+
+/* ---- joining branch shards that do not fit device memory, by key ranges ---------------------------------------------------------------------
+ * ipkgpu_db_join_files writes to out_path, byte for byte, the file that loading every path (ipkgpu_db_load), ipkgpu_db_join in the order
+ * of `paths`, ipkgpu_db_filter_mif0(J, total_num_groups, threshold) (filter = 0) or ipkgpu_db_filter_random(J) (filter = 1) and
+ * ipkgpu_db_write(J) under `h` write -- with no shard and no whole join ever resident (db_join_files.hpp).
+ * WHY IT COMPOSES: a key's joined list depends on that key's runs alone; MIF0 works per k-mer with the caller's N and the random filter
+ * draws per k-mer code, so filtering the join of a key range gives the values the whole join would; the files of disjoint key ranges,
+ * each in filter order, are merged by ipkgpu_db_merge_files into the bytes of the whole (the argument of the key-range build).
+ *
+ * Head checks, before any pass: IPKGPU_ERR_INVALID naming the file whose sequence type, k-mer size or omega bits are not h's, or whose
+ * positions flag is not the first file's (ipkgpu_db_union_files' wording).
+ *
+ * The plan is ipkgpu_db_diff_files', rule for rule, for S files in place of two.  avail = what "device_budget_bytes" leaves beside what
+ * the context holds, else the device's free memory; the context's cached result blocks and workspaces are given back first, after every
+ * range and on every return.  The window: "db_load_window_bytes", else avail / 16 clamped to 4 KiB .. 256 MiB, per file at most its
+ * body.  If range_bytes (below) at the heads' totals is at most avail -- or no shard holds a record -- there is ONE range [0, 2^32): no
+ * histogram pass, and the range is written straight to out_path (no range file, no directory, no host merge).  Otherwise one histogram
+ * pass per shard (db_stream_hist_kernel, 65 536 bins, shift = max(0, bits - 16)); one pair of device histograms is alive at a time,
+ * taken beside the budget, and copied to the host with the pass's n_w and L.  The ranges are cut greedily from bin 0 upward: a range is
+ * closed before the first bin whose addition would take range_bytes beyond avail; a bin that alone exceeds avail is IPKGPU_ERR_NOMEM
+ * before any range is loaded, the message naming the bin's key interval, the records and entries of every shard in it and the bytes
+ * needed.  The first range starts at 0, the last ends at 2^32.  (Every range of such a cut holds the bin that opened it, so it has a
+ * record; a range without one would be skipped: no load passes, no file.)
+ *
+ * Per range, ascending: for s = 0 .. S - 1 the key-range load of shard s with the counts expected from the histograms (more or fewer
+ * found: "the file changed between passes", IPKGPU_ERR_INVALID); ipkgpu_db_join over the S range databases in the order of `paths`,
+ * "join_route" honoured (a refusal of route 2 passes through with its message); the sources freed; the filter; the device writer into
+ * tmp_dir/range_%05u.ipk under `h`; J freed, everything cached given back.  Then ipkgpu_db_merge_files(h, range files) into out_path;
+ * the range files are removed, and tmp_dir too if the call created it (tmp_dir NULL: "<out_path>.ranges").  On every error the range
+ * files, a directory the call created and an output it began are removed, everything on the device is given back and the context
+ * stays usable.
+ *
+ * The writer's staging.  ipkgpu_db_write stages through two device buffers of min(256 MiB, body); here the piece is
+ * write_piece = avail / 16 clamped to 64 KiB .. 256 MiB, raised to longest_joined, a bound of the longest joined record:
+ * 16 + sum over s of (L_s - 16), L_s the longest record of shard s as its histogram pass saw it (0 for a shard without records); on
+ * the one-range shortcut L_s <= min(body, 16 + (8 or 10) * total entries) from the head.  The bytes written do not depend on the piece.
+ *
+ * Device memory, a true upper bound of what ipkgpu_mem_stats counts, from the terms defined for ipkgpu_db_diff_files_range_bytes
+ * (m, r, sort, scanx, db, load), ipkgpu_db_stream_window_bytes and ipkgpu_db_join_bytes.  fixed = the largest of the S files'
+ * ipkgpu_db_stream_window_bytes; N = sum n_s, E = sum e_s (J holds no more: duplicates only shrink it); body = 16 N + (8 or 10) E:
+ *   ipkgpu_db_join_files_range_bytes(fixed, S, n[], e[], pos, write_piece, longest_joined) =
+ *       max( max over s of  fixed + sum over t < s of db(n_t, e_t) + load(n_s, e_s),                          the loads
+ *            sum over s of db(n_s, e_s) + ipkgpu_db_join_bytes(N, E, S, pos),                                 the join
+ *            db(N, E) + 2 max(8 N, 16) + max(sort(N), 16),                                      the filter: two key arrays, the sort
+ *            db(N, E) + m(4 N) + m(8 (N + 1)) + 2 r(min(max(write_piece, longest_joined), body)) )    the write: sizes, offsets, staging
+ *       + scanx(N + 1)
+ * The whole call stays below the maximum of range_bytes over the ranges, and during a histogram pass below the figure given for
+ * ipkgpu_db_diff_files.
+ *
+ * Cost: S passes when one range fits, else S * (1 + R) for R ranges; a pass is one streamed read of a whole body with the host's walk,
+ * which bounds it; plus, with R ranges, one more write and read of the output (the range files and the host merge, which holds one open
+ * file and one 4-MiB buffer per range).
+ * The last call of a context, a refused one included: ipkgpu_db_join_files_num_ranges and _range; ipkgpu_db_join_files_stat: 0 = seconds in all, 1 = in the
+ * histogram passes, 2 = in the range loads, 3 = device ms in the joins (sum), 4 = body bytes read, 5 = passes over a body (all shards),
+ * 6 = seconds in the host's walk, 7 = seconds in filter and range writes, 8 = seconds in the final host merge, 9 = window bytes,
+ * 10 = avail, 11 = J-keys found in more than one source (sum; exact, the ranges are key-disjoint), 12 = entries dropped (sum),
+ * 13 = ranges that took route 1, 14 = the most device bytes the ranges held above what the context held when the call began (what
+ * range_bytes bounds; ipkgpu_mem_stats' peak also sees the histograms).  ipkgpu_db_join_files_range_bytes is host arithmetic (no GPU). */
+int ipkgpu_db_join_files(ipkgpu_ctx* ctx, const ipkgpu_db_header* h, const char* const* paths, uint32_t n_paths, int filter,
+                         uint64_t total_num_groups, float threshold, const char* out_path, const char* tmp_dir, uint64_t* total_kmers,
+                         uint64_t* total_entries, uint64_t* entries_dropped, uint64_t* bytes_written);
+uint64_t ipkgpu_db_join_files_range_bytes(uint64_t fixed, uint32_t n_srcs, const uint64_t* n, const uint64_t* e, int positioned,
+                                          uint64_t write_piece, uint64_t longest_joined);
+uint64_t ipkgpu_db_join_files_num_ranges(const ipkgpu_ctx* ctx);
+int ipkgpu_db_join_files_range(const ipkgpu_ctx* ctx, uint64_t i, uint64_t* key_lo, uint64_t* key_hi);
+double ipkgpu_db_join_files_stat(const ipkgpu_ctx* ctx, int which);
 
 #ifdef __cplusplus
 }

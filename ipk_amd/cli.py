@@ -718,9 +718,13 @@ def _join_num_nodes(head, num_tree_nodes):
                    "order of the files, one entry per branch with `put`'s maximum, and the join is filtered anew; --on device only")
 @click.option("--filter", "filter_", type=click.Choice(["mif0", "random"]), default="mif0", show_default=True, help="with --shared-keys: the filter of the output")
 @click.option("--num-tree-nodes", type=int, default=0, help="with --shared-keys: MIF0's N [the node count of the first shard's tree index]")
+@click.option("--stream", is_flag=True, default=False,
+              help="with --shared-keys: join by key ranges, no shard ever on the GPU whole: for shards that do not fit device memory together (same output)")
+@click.option("--budget-mib", type=float, default=None, help="with --stream: the device memory (MiB) the join may use on top of what the engine holds [what is free]")
+@click.option("--tmp-dir", default=None, type=click.Path(file_okay=False), help="with --stream: where the range files live until they are merged [OUTPUT.ranges]")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU index")
 @click.argument("shards", nargs=-1, required=True, type=click.Path(exists=True, dir_okay=False))
-def merge(output, on, shared_keys, filter_, num_tree_nodes, device, shards):
+def merge(output, on, shared_keys, filter_, num_tree_nodes, stream, budget_mib, tmp_dir, device, shards):
     """Joins database files with disjoint k-mer sets -- the shards of several ranks, the files of key-range passes, the batches of an
     on-disk build -- into one database file, its records in filter order.
 
@@ -731,8 +735,18 @@ def merge(output, on, shared_keys, filter_, num_tree_nodes, device, shards):
 
     --shared-keys joins files whose k-mer sets may overlap, in the order given: branch shards, built over different branch groups of
     one tree (`build --group-range`).  The shards of contiguous group ranges, given in range order and filtered as the build was,
-    give the whole build's file byte for byte.  The join needs every shard and the result in device memory; there is no host route."""
+    give the whole build's file byte for byte.  The join needs every shard and the result in device memory; there is no host route.
+
+    --shared-keys --stream is for shards that do not fit: the same file, joined by key ranges that each fit the device (or
+    --budget-mib) -- one histogram pass over every shard, then per range the shards' records of that range loaded, joined, filtered and
+    written as a range file under --tmp-dir; the host merge makes the output of the range files (ipkgpu_db_join_files)."""
     from ipk_amd import dbfile
+    if stream and not shared_keys:
+        raise click.UsageError("--stream goes with --shared-keys: shards with disjoint k-mer sets that do not fit are merged on the host (--on host)")
+    if (budget_mib is not None or tmp_dir is not None) and not stream:
+        raise click.UsageError("--budget-mib and --tmp-dir go with --stream")
+    if budget_mib is not None and not budget_mib > 0:
+        raise click.UsageError("--budget-mib must be positive")
     head = _shard_set_head(shards)
     if shared_keys:
         if on != "device":
@@ -741,6 +755,24 @@ def merge(output, on, shared_keys, filter_, num_tree_nodes, device, shards):
         import ipk_amd
         from ipk_amd.engine import ERR_NOMEM, IpkGpuError
         eng = ipk_amd.Engine(device)
+        if stream:
+            try:
+                if budget_mib is not None:
+                    eng.set_option("release_workspaces", 1)
+                    eng.set_option("device_budget_bytes", eng.mem_stats()[0] + int(budget_mib * (1 << 20)))
+                try:
+                    nk, ne, dropped = dbfile.join_shard_files_streamed(eng, output, head["sequence_type"], head["tree_index"], head["newick"], head["kmer_size"],
+                                                                       head["omega"], list(shards), filter_, n_nodes, tmp_dir=tmp_dir)
+                except IpkGpuError as e:
+                    if e.code != ERR_NOMEM:
+                        raise
+                    click.echo(f"merge: {e}", err=True)
+                    sys.exit(1)
+                n_ranges = len(eng.join_files_ranges())
+            finally:
+                eng.close()
+            click.echo(f"Output: {output} ({nk} k-mers, {ne} entries; merged on the device; {dropped} entries joined by put; joined in {n_ranges} key ranges)")
+            return
         try:
             nk, ne, dropped = dbfile.join_shard_files(eng, output, head["sequence_type"], head["tree_index"], head["newick"], head["kmer_size"],
                                                       head["omega"], list(shards), filter_, n_nodes)

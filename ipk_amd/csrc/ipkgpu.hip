@@ -190,6 +190,8 @@ struct ipkgpu_ctx {
     double t_union[4] = {0, 0, 0, 0};    // last ipkgpu_db_union, ms: all, key sort, entry copy, order sort (ipkgpu_db_union_time_ms)
     int64_t opt_join_route = 0;          // "join_route": 0 = the join decides whether duplicates can exist, 1 = it always resolves them, 2 = it refuses them
     double join_stat[7] = {0, 0, 0, 0, 0, 0, 0};   // last ipkgpu_db_join (ipkgpu_db_join_stat)
+    std::vector<uint64_t> jfiles_ranges;     // last ipkgpu_db_join_files: lo, hi of every range; jfiles_stat: ipkgpu_db_join_files_stat
+    double jfiles_stat[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // ipkgpu_db_place (db_place.hpp): a batch's sequences, offsets and results, the global S / C / touched tables, two counters;
     // place_amb: the per-window tables of ambiguous windows (ipkgpu_db_place_opts)
     DevBuf place_seq, place_off, place_out, place_tables, place_small, place_amb;
@@ -3054,7 +3056,10 @@ int ipkgpu_db_write_host_positions(const ipkgpu_db_header* h, uint64_t n_keys, c
     return IPKGPU_OK;
 }
 
-int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, const char* path, uint64_t* bytes_written)
+// ipkgpu_db_write with the bytes of a staged piece given (DB_WRITE_PIECE there): a piece is whole records, so it is raised to the longest
+// record; the bytes written do not depend on it.  ipkgpu_db_join_files writes its ranges in smaller pieces (db_join_files.hpp).
+constexpr uint64_t DB_WRITE_PIECE = (uint64_t)256 << 20;
+static int db_write_pieces(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, const char* path, uint64_t* bytes_written, uint64_t piece)
 {
     if (!ctx) return IPKGPU_ERR_INVALID;
     if (!db || db->ctx != ctx || !h || !path) return fail(ctx, IPKGPU_ERR_INVALID, "bad argument");
@@ -3111,7 +3116,7 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
         // pieces of whole records, two staging buffers: piece j+1 is packed and copied while piece j is written
         uint64_t max_rec = 0;
         for (uint64_t i = 0; i < n; ++i) max_rec = std::max(max_rec, rec_off[i + 1] - rec_off[i]);
-        const uint64_t PIECE = std::max<uint64_t>((uint64_t)256 << 20, max_rec);
+        const uint64_t PIECE = std::max<uint64_t>(piece, max_rec);
         void* d_stage[2] = {nullptr, nullptr};
         void* h_stage[2] = {nullptr, nullptr};
         hipEvent_t ev[2] = {nullptr, nullptr};
@@ -3163,6 +3168,11 @@ int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, c
     ctx->t_write_total = since(t_begin); ctx->t_write_device = t_dev; ctx->t_write_file = t_file;
     if (bytes_written) *bytes_written = total;
     return IPKGPU_OK;
+}
+
+int ipkgpu_db_write(ipkgpu_ctx* ctx, ipkgpu_db* db, const ipkgpu_db_header* h, const char* path, uint64_t* bytes_written)
+{
+    return db_write_pieces(ctx, db, h, path, bytes_written, DB_WRITE_PIECE);
 }
 
 }  // extern "C"
@@ -3470,4 +3480,5 @@ int ipkgpu_spill_merge(ipkgpu_ctx* ctx, uint32_t sigma, uint32_t k, uint32_t own
 #include "db_diff_files.hpp"
 #include "db_union.hpp"
 #include "db_join.hpp"
+#include "db_join_files.hpp"
 #include "comm_rccl.hpp"

@@ -379,3 +379,13 @@ def join_shard_files(engine, output, sequence_type, tree_index, newick, k, omega
         return db.num_keys, db.num_entries, dropped
     finally:
         db.free()
+
+
+def join_shard_files_streamed(engine, output, sequence_type, tree_index, newick, k, omega, paths, filter_, n_nodes, tmp_dir=None):
+    """join_shard_files for shards that do not fit device memory together (Engine.join_files, ipkgpu_db_join_files): the same file byte
+    for byte and the same return value, joined by key ranges that each fit "device_budget_bytes" (or the device's free memory) -- no
+    shard and no whole join is ever resident.  The range files live in tmp_dir (default: output + ".ranges") until the host merge has
+    made `output` of them.  IpkGpuError with code 3 when one key bin alone does not fit."""
+    from .engine import score_threshold
+    sigma = {"DNA": 4, "AA": 20}[sequence_type]
+    return engine.join_files(paths, output, sequence_type, tree_index, newick, k, omega, filter_, n_nodes, score_threshold(omega, sigma, k), tmp_dir=tmp_dir)

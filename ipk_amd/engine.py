@@ -1554,3 +1554,89 @@ def _join_stats(self):
 Engine.join_dbs = _join_dbs
 Engine.join_bytes = staticmethod(join_bytes)
 Engine.join_stats = _join_stats
+
+
+# ---- the join of branch shards that do not fit device memory, by key ranges (ipkgpu_db_join_files) -----------------------------------------
+
+ABI_SYMBOLS += ["ipkgpu_db_join_files", "ipkgpu_db_join_files_range_bytes", "ipkgpu_db_join_files_num_ranges", "ipkgpu_db_join_files_range",
+                "ipkgpu_db_join_files_stat"]
+
+JOIN_FILES_STATS = ("total_s", "hist_s", "loads_s", "join_ms", "body_bytes_read", "passes", "walk_s", "write_s", "merge_s", "window_bytes", "avail_bytes",
+                    "shared_keys", "entries_dropped", "route1_ranges", "range_peak_bytes")
+
+
+def _bind_join_files(L):
+    if getattr(L, "_join_files_bound", False):
+        return
+    from .dbfile import _Header
+    L.ipkgpu_db_join_files.restype = C.c_int
+    L.ipkgpu_db_join_files.argtypes = [C.c_void_p, C.POINTER(_Header), C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_uint64, C.c_float, C.c_char_p,
+                                       C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ipkgpu_db_join_files_range_bytes.restype = C.c_uint64
+    L.ipkgpu_db_join_files_range_bytes.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_uint64]
+    L.ipkgpu_db_join_files_num_ranges.restype = C.c_uint64
+    L.ipkgpu_db_join_files_num_ranges.argtypes = [C.c_void_p]
+    L.ipkgpu_db_join_files_range.restype = C.c_int
+    L.ipkgpu_db_join_files_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ipkgpu_db_join_files_stat.restype = C.c_double
+    L.ipkgpu_db_join_files_stat.argtypes = [C.c_void_p, C.c_int]
+    L._join_files_bound = True
+
+
+def join_files_range_bytes(fixed, n, e, positioned, write_piece, longest_joined):
+    """ipkgpu_db_join_files_range_bytes: the peak device bytes of joining, filtering and writing one key range of len(n) shards that hold
+    n[s] records and e[s] entries in it (the formula of include/ipkgpu.h; no GPU)."""
+    L = load_library()
+    _bind_join_files(L)
+    n, e = [int(x) for x in n], [int(x) for x in e]
+    assert len(n) == len(e)
+    arr = C.c_uint64 * max(len(n), 1)
+    return int(L.ipkgpu_db_join_files_range_bytes(int(fixed), len(n), arr(*n), arr(*e), int(bool(positioned)), int(write_piece), int(longest_joined)))
+
+
+def _join_files(self, paths, output, sequence_type, tree_index, newick, kmer_size, omega, filter_, n_nodes, threshold, tmp_dir=None):
+    """ipkgpu_db_join_files: the file that loading `paths`, join_dbs in that order, the filter (filter_ "mif0" with n_nodes = MIF0's N of
+    the WHOLE tree and the score threshold, or "random") and the device writer give, byte for byte, for shards that do not fit device
+    memory together: joined by key ranges planned against "device_budget_bytes" (or the device's free memory), the range files merged
+    on the host; tmp_dir (default: output + ".ranges") holds the range files meanwhile.  Returns (k-mers, entries, entries dropped)."""
+    from .dbfile import _header
+    if filter_ not in ("mif0", "random"):
+        raise ValueError(f"unknown filter {filter_!r} (mif0, random)")
+    _bind_keymajor(self._lib)
+    _bind_join_files(self._lib)
+    paths = [os.fspath(p) for p in paths]
+    h = _header(sequence_type, tree_index, newick, kmer_size, omega)
+    arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+    nk, ne, nd, nb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = self._lib.ipkgpu_db_join_files(self._h, C.byref(h), arr, len(paths), 0 if filter_ == "mif0" else 1, int(n_nodes), float(threshold),
+                                        os.fsencode(output), None if tmp_dir is None else os.fsencode(tmp_dir), C.byref(nk), C.byref(ne), C.byref(nd),
+                                        C.byref(nb))
+    if rc != 0:
+        raise self._err(rc)
+    return int(nk.value), int(ne.value), int(nd.value)
+
+
+def _join_files_ranges(self):
+    """[(lo, hi)] of the engine's last join_files."""
+    _bind_join_files(self._lib)
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    out = []
+    for i in range(int(self._lib.ipkgpu_db_join_files_num_ranges(self._h))):
+        self._lib.ipkgpu_db_join_files_range(self._h, i, C.byref(lo), C.byref(hi))
+        out.append((int(lo.value), int(hi.value)))
+    return out
+
+
+def _join_files_stats(self):
+    """The figures of JOIN_FILES_STATS for the engine's last join_files (ipkgpu_db_join_files_stat)."""
+    _bind_join_files(self._lib)
+    info = {k: float(self._lib.ipkgpu_db_join_files_stat(self._h, i)) for i, k in enumerate(JOIN_FILES_STATS)}
+    for k in ("body_bytes_read", "passes") + JOIN_FILES_STATS[9:]:
+        info[k] = int(info[k])
+    return info
+
+
+Engine.join_files = _join_files
+Engine.join_files_ranges = _join_files_ranges
+Engine.join_files_stats = _join_files_stats
+Engine.join_files_range_bytes = staticmethod(join_files_range_bytes)
